@@ -6,7 +6,15 @@ one get_jk on a synthetic diamond gth-dzvp-shaped cell, 4x4x4 k-mesh, nip = 600,
 36^3 FFT mesh.  AO values (PySCF's job in the reference)
 are evaluated once on the host and are resident in HBM before the timed region.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config c3|c2|c1] [--no-cpu-baseline]
+  python bench.py [--gpus N --steps K --warmup W] [--config c3|c2|c1] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] [--no-isolated]]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (value, ms_per_step,
+per-stage times and the roofline of the timed region, both read from the timed steps' own
+timers).  --dump-outputs DIR then writes what the last timed step returned (J, K) and built
+(interpolation points, W_0, a seeded sample of W_q) as DIR/<name>.npy.  --full adds the legs
+that take runs of their own: the untimed single-lane step (roofline.isolated), the GPU AO
+evaluator check (ao_eval) and the CPU oracle sample (cpu_baseline).
 
 For N > 1 the fitted q are sharded over N ranks, one process per GPU (RCCL all-to-all of y
 pieces, reduce-scatter of W_s rows, broadcast of W_0), and rank 0 prints one JSON line.  Under
@@ -53,10 +61,17 @@ def parse():
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the last step's outputs (vj, vk, perm, w0, "
+                        "wq_sample) as DIR/<name>.npy, float64, complex as (..., 2) re/im")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs outside the headline figure: the untimed single-lane "
+                        "step, the GPU AO evaluator check and the CPU oracle baseline")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: leave the CPU oracle baseline out")
     p.add_argument("--no-isolated", action="store_true",
-                   help="skip the untimed single-lane step (profiling runs: only warmup + timed "
-                        "steps reach the profiler)")
+                   help="with --full: skip the untimed single-lane step (profiling runs: only "
+                        "warmup + timed steps reach the profiler)")
     p.add_argument("--cpu-q", type=int, default=8, help="q-points fitted in the CPU sample")
     p.add_argument("--emulate-ranks", type=int, default=0, metavar="N",
                    help="time, on this one GPU, each rank's share of an N-rank k-sharded build "
@@ -154,6 +169,44 @@ def cpu_baseline(cell, kmesh, m0, c0, x0, chi, dm, nq):
                 cpu_share=int(share) if share and share.isdigit() else None,
                 fft_workers=R._fft_workers(), affinity_cpus=affinity, host_cpus=os.cpu_count(),
                 stages_s={k: round(v, 3) for k, v in t.items()})
+
+
+DUMP_CAP_BYTES = 12 << 20   # per array; five arrays stay under 64 MB in all
+
+
+def _as_f64(a):
+    """float64 copy of a host array; complex as a trailing (re, im) axis."""
+    a = np.ascontiguousarray(a)
+    if np.iscomplexobj(a):
+        a = a.astype(np.complex128, copy=False)
+        return a.view(np.float64).reshape(a.shape + (2,))
+    return a.astype(np.float64)
+
+
+def _sample_idx(n, itemsize):
+    """None if n items fit the cap, else a fixed (seed 0) sorted sample of flat indices."""
+    keep = DUMP_CAP_BYTES // itemsize
+    if n <= keep:
+        return None
+    return np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+
+
+def dump_outputs(path, df, vj, vk):
+    """What a caller of the timed step holds after its last repetition: J and K from get_jk,
+    and from build() the interpolation points, W_0 and (a sample of) this rank's fitted W_q."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    st = df._dev_state
+    out = {"vj": vj, "vk": vk, "perm": np.asarray(df.perm), "w0": st["W0"].cpu().numpy()}
+    for name, a in out.items():
+        a = np.asarray(a)
+        idx = _sample_idx(a.size, 16 if np.iscomplexobj(a) else 8)
+        np.save(os.path.join(path, name + ".npy"), _as_f64(a if idx is None else a.ravel()[idx]))
+    wq = st["Wq"].reshape(-1)
+    idx = _sample_idx(wq.numel(), 16)
+    if idx is not None:
+        wq = wq[torch.from_numpy(idx).to(wq.device)]
+    np.save(os.path.join(path, "wq_sample.npy"), _as_f64(wq.cpu().numpy()))
 
 
 def emulate_ranks(args):
@@ -363,7 +416,7 @@ def main():
     def step():
         df._dev_state = None
         df.build()
-        df.get_jk(dm)
+        return df.get_jk(dm)
 
     def barrier():
         torch.cuda.synchronize()
@@ -376,8 +429,10 @@ def main():
     d.ctx.call("fisdf_set_timing", 1)
     d.ctx.timings()  # reset
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        step()
+        last = None          # as before: the previous step's J, K are released before the next
+        last = step()
     barrier()
     dt = time.perf_counter() - t0
     stages = d.ctx.timings()
@@ -388,6 +443,9 @@ def main():
         dt = float(tt.item())
     ms_per_step = dt / args.steps * 1e3
     value = nk / (dt / args.steps)
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, df, *last)
+    del last
 
     # roofline of the dominant kernel.  The fit's two MFMA kernels per fitted q have the same
     # algorithmic work, 4 r^2 N flop (2 r^2 N for a self-conjugate q, real arithmetic):
@@ -445,7 +503,7 @@ def main():
     # include contention with the other lane's kernels; one extra untimed step with a single
     # lane gives each kernel's own rate
     iso_st = {k: (0.0, 0) for k in stages}
-    if not args.no_isolated:
+    if args.full and not args.no_isolated:
         d.ctx.call("fisdf_set_fit_lanes", 1)
         d.ctx.call("fisdf_set_timing", 1)
         d.ctx.timings()
@@ -475,21 +533,23 @@ def main():
     # input layer: Bloch AO values on the FFT grid by the GPU evaluator,
     # checked against the host restatement the timed steps used; outside the timed region
     # like the reference's own AO inputs (PySCF pbc_eval_gto)
-    from fisdf.ao import eval_ao_kpts_gpu
-    coords = cell.gen_uniform_grids(cell.mesh)
-    eval_ao_kpts_gpu(d, cell, coords, kmesh)
-    torch.cuda.synchronize()
-    t = time.perf_counter()
-    g = eval_ao_kpts_gpu(d, cell, coords, kmesh)
-    torch.cuda.synchronize()
-    ao = {"gpu_ms": round((time.perf_counter() - t) * 1e3, 3),
-          "cpu_s_host_restatement": round(getattr(setup, "ao_cpu_s", float("nan")), 3),
-          "max_rel_diff": float((g - df._ao_grid).abs().max() / df._ao_grid.abs().max()),
-          "note": "Bloch AOs on the FFT grid (nk, ngrid, nao); not in the timed steps"}
-    del g
+    ao = None
+    if args.full:
+        from fisdf.ao import eval_ao_kpts_gpu
+        coords = cell.gen_uniform_grids(cell.mesh)
+        eval_ao_kpts_gpu(d, cell, coords, kmesh)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        g = eval_ao_kpts_gpu(d, cell, coords, kmesh)
+        torch.cuda.synchronize()
+        ao = {"gpu_ms": round((time.perf_counter() - t) * 1e3, 3),
+              "cpu_s_host_restatement": round(getattr(setup, "ao_cpu_s", float("nan")), 3),
+              "max_rel_diff": float((g - df._ao_grid).abs().max() / df._ao_grid.abs().max()),
+              "note": "Bloch AOs on the FFT grid (nk, ngrid, nao); not in the timed steps"}
+        del g
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         chi = __import__("fisdf").cell.eval_ao_kpts(cell, cell.gen_uniform_grids(cell.mesh), kmesh)
         cpu = cpu_baseline(cell, kmesh, m0, c0, x0, chi, dm, args.cpu_q)
         del chi

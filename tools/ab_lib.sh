@@ -5,7 +5,7 @@ set -o pipefail
 for v in "$@"; do
   [ "$v" = "default" ] && v=""
   FISDF_LIB_VARIANT=$v timeout -k 10 200 python tools/gemm_bench.py --quick --fx || exit 1
-  FISDF_LIB_VARIANT=$v timeout -k 10 300 python -u bench.py --no-cpu-baseline > /tmp/abl.json || exit 1
+  FISDF_LIB_VARIANT=$v timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > /tmp/abl.json || exit 1
   python - "lib '$v'" /tmp/abl.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2]))

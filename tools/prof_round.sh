@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round profile of the C3 bench on one MI355X: the default bench line (with CPU baseline), a
+# Round profile of the C3 bench on one MI355X: the --full bench line (with CPU baseline), a
 # rocprofv3 kernel trace of the warmup + timed steps only (--no-isolated: the untimed single-lane
 # step is left out, so the CSV's per-step kernel time matches the bench's roofline), and
 # FETCH_SIZE / WRITE_SIZE passes (separate runs) for the roofline kernels' HBM traffic.
@@ -13,7 +13,7 @@ TAG=${1:-prof}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 400 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH FAILED; tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH FAILED; tail -20 $OUT/bench.err; exit 1; }
 cat $OUT/bench.json
 ok() { local rc=$1 dir=$2 pat=$3; echo "pass $dir rc=$rc"; [ $rc -ne 124 ] && [ $rc -ne 137 ] && [ -n "$(find $dir -name "$pat" 2>/dev/null)" ]; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py --no-cpu-baseline --no-isolated > $OUT/trace.json 2> $OUT/trace.err
