@@ -10,7 +10,9 @@
 // at ~75 % of the FP64 MFMA pipe (profiles/r02_pmc_gemm_summary.txt) are halved or better.
 // op(A) = A (N, [m][k], K-contiguous: XOR-swizzled LDS image), op(B) = B (N, [k][n]).
 // MODE: GEMM_FULL, GEMM_A_REAL (Im A = 0: 2 MFMAs per block), GEMM_A_LOWER (A lower
-// triangular: each M-tile stops its K loop at its last row; longest tiles dispatched first).
+// triangular: each M-tile stops its K loop at its last row, and over its diagonal 64 x 64 square
+// of A only the 16-row blocks that still hold nonzeros issue MFMAs; longest tiles dispatched
+// first; the caller passes exact zeros above the diagonal).
 // XCD-aware order as in zgemm.hip: XCD x owns a contiguous chunk of (M-tile fastest, N-panel)
 // order, so the M-tiles sharing one 128-column panel of B read it from that XCD's L2.
 #include "common.h"
@@ -21,6 +23,12 @@ namespace {
 
 #ifndef FISDF_WIDE_PIPE
 #define FISDF_WIDE_PIPE 1
+#endif
+// 1: an A_LOWER tile's last K-steps (its diagonal 64 x 64 square of A) issue MFMAs only for the
+// 16-row blocks that still hold nonzeros there.  0: every block runs to the tile's last column
+// (A/B builds: tools/build_variant.sh).
+#ifndef FISDF_WIDE_DIAGSKIP
+#define FISDF_WIDE_DIAGSKIP 1
 #endif
 
 constexpr int WBM = 64, WBN = 128, WBK = 8;
@@ -52,8 +60,17 @@ __global__ __launch_bounds__(256, 2) void zgemm_nn_wide_kernel(
   // instead of leaving the lower two waves idle
   const int vr = min(4, max(0, (M - m0 + 15) / 16));
   const bool edge = vr <= 2;
-  const int wm = edge ? 0 : (w >> 1) * 32;
-  const int wn = edge ? 32 * w : (w & 1) * 64;
+  const int wu = __builtin_amdgcn_readfirstlane(w);
+  // DIAG (pipelined A_LOWER): every wave owns all the tile's 16-row blocks (4, or 2 on an M-edge
+  // tile) x 32 columns (4 x 2 blocks of C instead of 2 x 4: the same MFMAs, fragment reads and
+  // operand additions per K-substep), so that in the tile's diagonal section, where the row
+  // blocks run out of nonzeros one after the other, all four waves drop the same MFMAs in the
+  // same K-steps and meet each barrier with equal work behind them
+  constexpr bool DIAG = FISDF_WIDE_PIPE && FISDF_WIDE_DIAGSKIP && (MODE & GEMM_A_LOWER) != 0;
+  const int wm = DIAG || edge ? 0 : (w >> 1) * 32;
+  const int wn = DIAG ? 32 * wu : edge ? 32 * w : (w & 1) * 64;
+  // accumulator block (mi, ni) of the wave
+  auto ix = [](int mi, int ni) { return DIAG ? mi * 2 + ni : mi * 4 + ni; };
 
   // LDS-DMA sources.  A stage: slot sl = row x * 8 + k' holds A[m0 + x][k0 + (k' ^ (x & 7))];
   // B stage: slot sl = k * 128 + x holds B[k0 + k][n0 + x].  Rows / columns outside the matrix
@@ -103,15 +120,13 @@ __global__ __launch_bounds__(256, 2) void zgemm_nn_wide_kernel(
   constexpr bool AREAL = (MODE & GEMM_A_REAL) != 0;
   // FULL: accR = P1 = ar br, accI = P2 = ai bi, acc3 = P3 = (ar + ai)(br + bi); after the K loop
   // Re = P1 - P2, Im = P3 - P1 - P2.  A_REAL: accR = ar br, accI = ar bi.
-  f64x4 accR[2][4], accI[2][4], acc3[AREAL ? 1 : 2][AREAL ? 1 : 4];
+  f64x4 accR[8], accI[8], acc3[AREAL ? 1 : 8];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      accR[i][j] = f64x4{0, 0, 0, 0};
-      accI[i][j] = f64x4{0, 0, 0, 0};
-      if constexpr (!AREAL) acc3[i][j] = f64x4{0, 0, 0, 0};
-    }
+  for (int i = 0; i < 8; ++i) {
+    accR[i] = f64x4{0, 0, 0, 0};
+    accI[i] = f64x4{0, 0, 0, 0};
+    if constexpr (!AREAL) acc3[i] = f64x4{0, 0, 0, 0};
+  }
 
   const int nsteps = kend > 0 ? (kend + WBK - 1) / WBK : 0;
   const int i16 = lane & 15, kq = lane >> 4;
@@ -143,7 +158,6 @@ __global__ __launch_bounds__(256, 2) void zgemm_nn_wide_kernel(
     oB[j] = (unsigned)(((long)k * ldb + min(n0 + x, N - 1)) * 16);
   }
   const long dBs = (long)WBK * ldb;
-  const int wu = __builtin_amdgcn_readfirstlane(w);
   auto gldss = [&](const cplx* base, unsigned off, unsigned lds_byte) {
     unsigned keep;
     const unsigned dst = __builtin_amdgcn_readfirstlane(lds_byte);
@@ -161,8 +175,8 @@ __global__ __launch_bounds__(256, 2) void zgemm_nn_wide_kernel(
 #pragma unroll
     for (int j = 0; j < LPB; ++j) gldss(bb, oB[j], lb + (unsigned)((wu * LPB + j) * 64) * 16u);
   };
-  auto pipeloop = [&](auto nbc) {
-    constexpr int NB = decltype(nbc)::value;
+  auto pipeloop = [&](auto mbc, auto nbc) {
+    constexpr int MB = decltype(mbc)::value, NB = decltype(nbc)::value;  // blocks per wave
     if (nsteps == 0) return;
 #pragma unroll
     for (int st = 0; st < NS - 1; ++st)
@@ -172,69 +186,100 @@ __global__ __launch_bounds__(256, 2) void zgemm_nn_wide_kernel(
     else
       asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    cplx fa[2], fb[NB];
-    auto rd = [&](int slot, int kk) {
+    cplx fa[MB], fb[NB];
+    // mk: the wave's live row blocks (bit u: fa[u] feeds MFMAs); all of them everywhere but in
+    // the diagonal section of an A_LOWER tile (below)
+    using Full = std::integral_constant<int, (1 << MB) - 1>;
+    // DIAG: per-lane fragment slots within a stage (A at K-substep 0 / 1 of row block 0, B),
+    // named so that the K loops below share them
+    const int a0 = i16 * WBK + (kq ^ (i16 & (WBK - 1)));
+    const int a1 = i16 * WBK + ((4 + kq) ^ (i16 & (WBK - 1)));
+    const int bo = kq * WBN + wn + i16;
+    auto rd = [&](int slot, int kk, auto mk) {
+      constexpr int MK = decltype(mk)::value;
       const cplx* as = sm + (long)slot * (TA + TB);
       const cplx* bs = as + TA;
-      const int k = kk + kq;
+      if constexpr (DIAG) {
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int x = wm + u * 16 + i16;
-        fa[u] = as[x * WBK + (k ^ (x & (WBK - 1)))];
+        for (int u = 0; u < MB; ++u)
+          if (MK >> u & 1) fa[u] = as[(kk ? a1 : a0) + u * 16 * WBK];
+        if constexpr (MK != 0) {
+#pragma unroll
+          for (int u = 0; u < NB; ++u) fb[u] = bs[bo + kk * WBN + u * 16];
+        }
+      } else {
+        const int k = kk + kq;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int x = wm + u * 16 + i16;
+          fa[u] = as[x * WBK + (k ^ (x & (WBK - 1)))];
+        }
+#pragma unroll
+        for (int u = 0; u < NB; ++u) fb[u] = bs[k * WBN + wn + u * 16 + i16];
       }
-#pragma unroll
-      for (int u = 0; u < NB; ++u) fb[u] = bs[k * WBN + wn + u * 16 + i16];
     };
-    rd(0, 0);
+    rd(0, 0, Full{});
     if (NS - 1 < nsteps) issue_p(NS - 1);
-    double sa[2], sb[NB];
-    auto p12 = [&]() {
+    double sa[MB], sb[NB];
+    auto p12 = [&](auto mk) {
+      constexpr int MK = decltype(mk)::value;
 #pragma unroll
-      for (int u = 0; u < 2; ++u) sa[u] = fa[u].x + fa[u].y;
+      for (int u = 0; u < MB; ++u)
+        if (MK >> u & 1) sa[u] = fa[u].x + fa[u].y;
+      if constexpr (MK != 0) {
 #pragma unroll
-      for (int u = 0; u < NB; ++u) sb[u] = fb[u].x + fb[u].y;
+        for (int u = 0; u < NB; ++u) sb[u] = fb[u].x + fb[u].y;
+      }
       if constexpr (AREAL) {
 #pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
+        for (int mi = 0; mi < MB; ++mi)
 #pragma unroll
           for (int ni = 0; ni < NB; ++ni)
-            accR[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[mi].x, fb[ni].x, accR[mi][ni], 0, 0, 0);
+            if (MK >> mi & 1)
+              accR[ix(mi, ni)] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[mi].x, fb[ni].x, accR[ix(mi, ni)], 0, 0, 0);
 #pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
+        for (int mi = 0; mi < MB; ++mi)
 #pragma unroll
           for (int ni = 0; ni < NB; ++ni)
-            accI[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[mi].x, fb[ni].y, accI[mi][ni], 0, 0, 0);
+            if (MK >> mi & 1)
+              accI[ix(mi, ni)] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[mi].x, fb[ni].y, accI[ix(mi, ni)], 0, 0, 0);
       } else {
 #pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
+        for (int mi = 0; mi < MB; ++mi)
 #pragma unroll
           for (int ni = 0; ni < NB; ++ni)
-            accR[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[mi].x, fb[ni].x, accR[mi][ni], 0, 0, 0);
+            if (MK >> mi & 1)
+              accR[ix(mi, ni)] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[mi].x, fb[ni].x, accR[ix(mi, ni)], 0, 0, 0);
 #pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
+        for (int mi = 0; mi < MB; ++mi)
 #pragma unroll
           for (int ni = 0; ni < NB; ++ni)
-            accI[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[mi].y, fb[ni].y, accI[mi][ni], 0, 0, 0);
+            if (MK >> mi & 1)
+              accI[ix(mi, ni)] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[mi].y, fb[ni].y, accI[ix(mi, ni)], 0, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
     };
-    auto p3 = [&]() {
+    auto p3 = [&](auto mk) {
+      constexpr int MK = decltype(mk)::value;
       if constexpr (!AREAL) {
 #pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
+        for (int mi = 0; mi < MB; ++mi)
 #pragma unroll
           for (int ni = 0; ni < NB; ++ni)
-            acc3[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(sa[mi], sb[ni], acc3[mi][ni], 0, 0, 0);
+            if (MK >> mi & 1)
+              acc3[ix(mi, ni)] = __builtin_amdgcn_mfma_f64_16x16x4f64(sa[mi], sb[ni], acc3[ix(mi, ni)], 0, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
     };
-    for (int s = 0; s < nsteps; ++s) {
+    // one K-step; mk: the wave's live row blocks in it.  The fragments read ahead for the next
+    // step use the same mask: a block dead in this step stays dead to the tile's end.
+    auto kstep = [&](int s, auto mk) {
       const int cur = s % NS;
-      p12();
-      rd(cur, 4);
+      p12(mk);
+      rd(cur, 4, mk);
       __builtin_amdgcn_sched_barrier(0);
-      p3();
-      p12();
+      p3(mk);
+      p12(mk);
       if (s + 1 < nsteps) {
         // step s+1 landed (step s+2's pieces may stay in flight) and every wave is done with
         // step s's slot, which issue_p(s + NS) refills
@@ -243,17 +288,47 @@ __global__ __launch_bounds__(256, 2) void zgemm_nn_wide_kernel(
         else
           asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        rd((s + 1) % NS, 0);
+        rd((s + 1) % NS, 0, mk);
         if (s + NS < nsteps) issue_p(s + NS);
         __builtin_amdgcn_sched_barrier(0);
       }
-      p3();
+      p3(mk);
+    };
+    if constexpr (DIAG) {
+      // Diagonal section: the K-steps over the tile's 64 x 64 square of A (k >= m0).  Row block b
+      // holds nonzeros in the square's columns < 16 (b + 1) only, so it is live in K-steps
+      // s < m0 / 8 + 2 (b + 1).  K loops in sequence, each with its compile-time mask and
+      // wave-uniform scalar bounds: all blocks (the body and the square's first two K-steps),
+      // then one block fewer every two K-steps.  Every wave still issues all its LDS-DMA pieces
+      // and meets every barrier with the same counts: only MFMAs, and the fragment reads and
+      // operand additions that would feed none, are dropped (products 0 * b on the zeros above
+      // the diagonal).
+      const int sd = m0 / WBK;
+      int s = 0;
+      auto run = [&](int lim, auto mk) {
+        for (const int e = min(lim, nsteps); s < e; ++s) kstep(s, mk);
+      };
+      run(sd + 2, Full{});
+      if constexpr (MB == 4) {
+        run(sd + 4, std::integral_constant<int, 0xE>{});
+        run(sd + 6, std::integral_constant<int, 0xC>{});
+        run(nsteps, std::integral_constant<int, 0x8>{});
+      } else {
+        run(sd + 4, std::integral_constant<int, 2>{});
+        run(nsteps, std::integral_constant<int, 0>{});
+      }
+    } else {
+      for (int s = 0; s < nsteps; ++s) kstep(s, Full{});
     }
   };
+  using I2 = std::integral_constant<int, 2>;
+  using I4 = std::integral_constant<int, 4>;
   if (edge)
-    pipeloop(std::integral_constant<int, 2>{});
+    pipeloop(I2{}, I2{});
+  else if constexpr (DIAG)
+    pipeloop(I4{}, I2{});
   else
-    pipeloop(std::integral_constant<int, 4>{});
+    pipeloop(I2{}, I4{});
 #else
   if (nsteps > 0) {
 #pragma unroll
@@ -294,12 +369,12 @@ __global__ __launch_bounds__(256, 2) void zgemm_nn_wide_kernel(
           for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
             for (int ni = 0; ni < NB; ++ni)
-              accR[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[mi], br[ni], accR[mi][ni], 0, 0, 0);
+              accR[ix(mi, ni)] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[mi], br[ni], accR[ix(mi, ni)], 0, 0, 0);
 #pragma unroll
           for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
             for (int ni = 0; ni < NB; ++ni)
-              accI[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[mi], bi[ni], accI[mi][ni], 0, 0, 0);
+              accI[ix(mi, ni)] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[mi], bi[ni], accI[ix(mi, ni)], 0, 0, 0);
         } else {
           double sa[2], sb[NB];
 #pragma unroll
@@ -310,17 +385,17 @@ __global__ __launch_bounds__(256, 2) void zgemm_nn_wide_kernel(
           for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
             for (int ni = 0; ni < NB; ++ni)
-              accR[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[mi], br[ni], accR[mi][ni], 0, 0, 0);
+              accR[ix(mi, ni)] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[mi], br[ni], accR[ix(mi, ni)], 0, 0, 0);
 #pragma unroll
           for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
             for (int ni = 0; ni < NB; ++ni)
-              accI[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai[mi], bi[ni], accI[mi][ni], 0, 0, 0);
+              accI[ix(mi, ni)] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai[mi], bi[ni], accI[ix(mi, ni)], 0, 0, 0);
 #pragma unroll
           for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
             for (int ni = 0; ni < NB; ++ni)
-              acc3[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(sa[mi], sb[ni], acc3[mi][ni], 0, 0, 0);
+              acc3[ix(mi, ni)] = __builtin_amdgcn_mfma_f64_16x16x4f64(sa[mi], sb[ni], acc3[ix(mi, ni)], 0, 0, 0);
         }
       }
     }
@@ -332,13 +407,13 @@ __global__ __launch_bounds__(256, 2) void zgemm_nn_wide_kernel(
 #endif
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the zero-page pieces in flight
 
-  const int nb = edge ? 2 : 4;
+  const int mb = DIAG && !edge ? 4 : 2, nb = DIAG || edge ? 2 : 4;
   const bool use_beta = beta.x != 0.0 || beta.y != 0.0;
 #pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
+  for (int mi = 0; mi < (DIAG ? 4 : 2); ++mi)
 #pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      if (ni >= nb) continue;
+    for (int ni = 0; ni < (DIAG ? 2 : 4); ++ni) {
+      if (mi >= mb || ni >= nb) continue;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = m0 + wm + mi * 16 + (lane >> 4) + 4 * r;
@@ -346,10 +421,10 @@ __global__ __launch_bounds__(256, 2) void zgemm_nn_wide_kernel(
         if (row < M && col < N) {
           double re, im;
           if constexpr (AREAL) {
-            re = accR[mi][ni][r];
-            im = accI[mi][ni][r];
+            re = accR[ix(mi, ni)][r];
+            im = accI[ix(mi, ni)][r];
           } else {
-            const double p1 = accR[mi][ni][r], p2 = accI[mi][ni][r], p3 = acc3[mi][ni][r];
+            const double p1 = accR[ix(mi, ni)][r], p2 = accI[ix(mi, ni)][r], p3 = acc3[ix(mi, ni)][r];
             re = p1 - p2;
             im = p3 - p1 - p2;
           }
