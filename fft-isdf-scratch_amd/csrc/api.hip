@@ -994,6 +994,65 @@ int fisdf_herk(fisdf_ctx* c, int n, int K, double alpha, const void* A, long lda
   return herk(c->stream, n, K, alpha, (const cplx*)A, lda, (cplx*)Cm, ldc, ksplit, work);
 }
 
+int fisdf_zgemm_ex(fisdf_ctx* c, int opA, int opB, int M, int N, int K, const double alpha[2],
+                   const void* A, long lda, long sA, const void* B, long ldb, long sB,
+                   const double beta[2], void* C, long ldc, long sC, int batch, int ksplit,
+                   int mode, int epi, const void* aux, long ldaux, double* h_mon) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(epi == EPI_NONE || epi == EPI_STREAM || epi == EPI_CSQUARE || epi == EPI_REAL ||
+                  epi == EPI_WSRHO,
+              "zgemm_ex: unknown epilogue");
+  FISDF_CHECK(epi == EPI_NONE || (beta[0] == 0.0 && beta[1] == 0.0),
+              "zgemm_ex: the epilogues take beta = 0");
+  FISDF_CHECK(epi != EPI_REAL || batch <= 1, "zgemm_ex: EPI_REAL takes one batch");
+  FISDF_CHECK(epi != EPI_WSRHO || (aux != nullptr && ldaux >= N),
+              "zgemm_ex: EPI_WSRHO needs the real aux matrix (ldaux >= N)");
+  // the epilogue's max |Im| goes to the context's fourth monitor word: fisdf_max_imag reports
+  // the first three (the product's), which this call leaves alone
+  const bool monitored = epi == EPI_CSQUARE || epi == EPI_REAL || epi == EPI_WSRHO;
+  unsigned long long* mon = monitored ? c->maximag + 3 : nullptr;
+  if (mon) FISDF_HIP(hipMemsetAsync(mon, 0, sizeof(unsigned long long), c->stream));
+  cplx* work = nullptr;
+  if (epi == EPI_WSRHO) {
+    work = (cplx*)const_cast<void*>(aux);
+  } else if (epi == EPI_NONE && ksplit > 1 && M > 0 && N > 0 && batch > 0) {
+    void* w;
+    FISDF_TRY(arena_get(c, sizeof(cplx) * (size_t)ksplit * M * N * batch, &w));
+    work = (cplx*)w;
+  }
+  FISDF_TRY(zgemm(c->stream, opA, opB, M, N, K, cmk(alpha[0], alpha[1]), (const cplx*)A, lda, sA,
+                  (const cplx*)B, ldb, sB, cmk(beta[0], beta[1]), (cplx*)C, ldc, sC, batch, ksplit,
+                  work, epi, mon, mode, ldaux));
+  if (h_mon) {
+    *h_mon = 0.0;
+    if (mon) {
+      unsigned long long h = 0;
+      FISDF_HIP(hipMemcpyAsync(&h, mon, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+      FISDF_HIP(hipStreamSynchronize(c->stream));
+      std::memcpy(h_mon, &h, sizeof(double));
+    }
+  }
+  return 0;
+}
+
+int fisdf_herk_ex(fisdf_ctx* c, int n, int K, double alpha, const void* A, long lda, long sA,
+                  double beta, void* Cm, long ldc, long sC, int batch, int ksplit, int mode) {
+  FISDF_TRY(device_guard(c));
+  if (batch == 1 && beta == 0.0) {
+    cplx* work = nullptr;
+    if (ksplit > 1 && n > 0) {
+      void* w;
+      FISDF_TRY(arena_get(c, sizeof(cplx) * (size_t)ksplit * n * n, &w));
+      work = (cplx*)w;
+    }
+    return herk(c->stream, n, K, alpha, (const cplx*)A, lda, (cplx*)Cm, ldc, ksplit, work, mode);
+  }
+  FISDF_CHECK(ksplit <= 1, "herk_ex: the batched / beta != 0 HERK has no split-K");
+  FISDF_CHECK(mode == GEMM_FULL, "herk_ex: the batched / beta != 0 HERK has mode FULL only");
+  return herk_batched(c->stream, n, K, alpha, (const cplx*)A, lda, sA, beta, (cplx*)Cm, ldc, sC,
+                      batch);
+}
+
 int fisdf_fft3d(fisdf_ctx* c, const void* in, void* out, int rows, const int mesh[3]) {
   FISDF_TRY(device_guard(c));
   long ng = (long)mesh[0] * mesh[1] * mesh[2];

@@ -103,7 +103,9 @@ enum Epi { EPI_NONE = 0, EPI_STREAM = 2, EPI_CSQUARE = 4, EPI_REAL = 5, EPI_WSRH
 // GEMM_A_LOWER: op(A) = A (OP_N) is lower triangular: each M-tile stops its K loop at the
 // tile's last row (the zero upper part is never read or multiplied).
 // GEMM_A_UPPER: op(A) = A^H (OP_C) is upper triangular (A lower): each M-tile starts its K loop
-// at its own first row (no split-K)
+// at its own first row.  (C,N) and (C,C) only.  With split-K a split whose K range lies wholly
+// left of an M-tile's first row runs no K-step and writes a zero partial, which the reduction
+// sums like any other.
 enum GemmMode { GEMM_FULL = 0, GEMM_A_REAL = 1, GEMM_RE_ONLY = 2, GEMM_A_LOWER = 4, GEMM_A_UPPER = 8 };
 int zgemm(hipStream_t s, int opA, int opB, int M, int N, int K, cplx alpha,
           const cplx* A, long lda, long sA, const cplx* B, long ldb, long sB, cplx beta,

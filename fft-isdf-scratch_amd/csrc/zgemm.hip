@@ -716,8 +716,8 @@ int zgemm(hipStream_t s, int opA, int opB, int M, int N, int K, cplx alpha, cons
               "zgemm: real modes are implemented for (N,N) and (C,N) only");
   // GEMM_A_UPPER with split-K: a split whose K range lies wholly left of an M-tile's first row
   // runs no K-step and writes a zero partial (the reduce sums every split)
-  FISDF_CHECK(mode != GEMM_A_UPPER || opA == OP_C,
-              "zgemm: GEMM_A_UPPER is implemented for op(A) = A^H");
+  FISDF_CHECK(mode != GEMM_A_UPPER || (opA == OP_C && (opB == OP_N || opB == OP_C)),
+              "zgemm: GEMM_A_UPPER is implemented for (C,N) and (C,C) only");
   FISDF_CHECK(!(mode & GEMM_A_LOWER) || (opA == OP_N && opB == OP_N && !(mode & GEMM_RE_ONLY)),
               "zgemm: GEMM_A_LOWER is implemented for (N,N), optionally with GEMM_A_REAL");
   if (M == 0 || N == 0 || batch == 0) return 0;
@@ -736,6 +736,7 @@ int zgemm(hipStream_t s, int opA, int opB, int M, int N, int K, cplx alpha, cons
               "zgemm: too many tiles");
   dim3 grid((N + BN - 1) / BN, (M + BM - 1) / BM, batch * ksplit);
   const CallEvents ev;
+  bool launched = mode == GEMM_FULL;  // every op pair has a FULL kernel (the switch below)
 #define FISDF_CASE(a, b)                                                                      \
   case a * 4 + b:                                                                             \
     launch<a, b>(s, grid, M, N, K, alpha, A, lda, sA, B, ldb, sB, beta, C, ldc, sC, ksplit,   \
@@ -745,12 +746,15 @@ int zgemm(hipStream_t s, int opA, int opB, int M, int N, int K, cplx alpha, cons
   if (opA == a && opB == b && mode == m) {                                                    \
     launch<a, b, false, m>(s, grid, M, N, K, alpha, A, lda, sA, B, ldb, sB, beta, C, ldc, sC, \
                            ksplit, kchunk, work, epi, mon, ldaux, ev.span);         \
+    launched = true;                                                                          \
   }
   FISDF_MCASE(0, 0, 1) FISDF_MCASE(0, 0, 2) FISDF_MCASE(0, 0, 3)
   FISDF_MCASE(0, 0, 4) FISDF_MCASE(0, 0, 5)
   FISDF_MCASE(3, 0, 1) FISDF_MCASE(3, 0, 2) FISDF_MCASE(3, 0, 3)
   FISDF_MCASE(3, 0, 8) FISDF_MCASE(3, 3, 8)
 #undef FISDF_MCASE
+  // a mode the checks above let through but no instantiation matches must not return as if done
+  FISDF_CHECK(launched, "zgemm: no kernel for this (opA, opB, mode)");
   if (mode == GEMM_FULL) switch (opA * 4 + opB) {
     FISDF_CASE(0, 0) FISDF_CASE(0, 1) FISDF_CASE(0, 2) FISDF_CASE(0, 3)
     FISDF_CASE(1, 0) FISDF_CASE(1, 1) FISDF_CASE(1, 2) FISDF_CASE(1, 3)

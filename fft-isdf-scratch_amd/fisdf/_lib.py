@@ -91,6 +91,9 @@ _SIGS = {
                      _i, _i], _i),
     "fisdf_zgemm_mode": ([_vp, _i, _i, _i, _i, _i, _dp, _vp, _l, _l, _vp, _l, _l, _dp, _vp, _l,
                           _l, _i, _i], _i),
+    "fisdf_zgemm_ex": ([_vp, _i, _i, _i, _i, _i, _dp, _vp, _l, _l, _vp, _l, _l, _dp, _vp, _l, _l,
+                        _i, _i, _i, _i, _vp, _l, _dp], _i),
+    "fisdf_herk_ex": ([_vp, _i, _i, _d, _vp, _l, _l, _d, _vp, _l, _l, _i, _i, _i], _i),
     "fisdf_herk": ([_vp, _i, _i, _d, _vp, _l, _vp, _l, _i], _i),
     "fisdf_fft3d": ([_vp, _vp, _vp, _i, _ip], _i),
     "fisdf_fft3d_paired": ([_vp, _vp, _vp, _i, _ip, _dp, _ip, _i], _i),

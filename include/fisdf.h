@@ -506,6 +506,25 @@ int fisdf_zgemm_mode(fisdf_ctx* ctx, int opA, int opB, int M, int N, int K, cons
                      const void* d_A, long lda, long strideA, const void* d_B, long ldb,
                      long strideB, const double beta[2], void* d_C, long ldc, long strideC,
                      int batch, int mode);
+/* everything the library's GEMM takes, for tests of its dispatch: split-K (workspace from the
+ * context's arena) together with a mode, and the fused epilogues: epi 0 none, 2 = C = alpha acc
+ * with streaming stores, 4 = C = (alpha acc)^2 elementwise, 5 = C = Re(alpha acc) written as
+ * doubles (d_C is a double*, ldc in doubles, one batch), 6 = C = d_aux * Re(alpha acc) + 0i with
+ * d_aux real (doubles, row stride ldaux).  The epilogues take beta = 0 and no split-K.  h_mon
+ * (host, may be NULL) receives max |Im(alpha acc)| of epilogues 4, 5, 6 (0 otherwise); it is kept
+ * in a device word of its own, so what fisdf_max_imag reports does not change. */
+int fisdf_zgemm_ex(fisdf_ctx* ctx, int opA, int opB, int M, int N, int K, const double alpha[2],
+                   const void* d_A, long lda, long strideA, const void* d_B, long ldb,
+                   long strideB, const double beta[2], void* d_C, long ldc, long strideC,
+                   int batch, int ksplit, int mode, int epi, const void* d_aux, long ldaux,
+                   double* h_mon);
+/* C[b] = alpha A[b] A[b]^H + beta C[b] with real alpha, beta.  batch == 1 and beta == 0: the
+ * HERK with split-K and mode 0 (full) or 2 (C = alpha Re(A A^H)); anything else: the batched
+ * HERK (lower tiles + mirror of a Hermitian C), which has no split-K and mode 0 only (an error
+ * otherwise) */
+int fisdf_herk_ex(fisdf_ctx* ctx, int n, int K, double alpha, const void* d_A, long lda,
+                  long strideA, double beta, void* d_C, long ldc, long strideC, int batch,
+                  int ksplit, int mode);
 /* C = alpha A A^H (A: n x K, lda; C: n x n, ldc), Hermitian: lower tiles + mirror */
 int fisdf_herk(fisdf_ctx* ctx, int n, int K, double alpha, const void* d_A, long lda, void* d_C,
                long ldc, int ksplit);
