@@ -1070,6 +1070,38 @@ int fisdf_fft3d_paired(fisdf_ctx* c, const void* in, void* out, int rows, const 
                mesh[2], kd, nullptr, nullptr, nullptr, m, in_real != 0);
 }
 
+int fisdf_fft3d_ex(fisdf_ctx* c, const void* in, long in_ld, const int* rowidx, void* out,
+                   long out_ld, int rows, const int mesh[3], const double* h_kd,
+                   const double* weight, const long* h_plane_base, const long* h_plane_ld,
+                   const int* h_m, int in_real, int* h_path) {
+  FISDF_TRY(device_guard(c));
+  if (h_path) *h_path = -1;
+  FISDF_CHECK(in && out && mesh && rows >= 0, "fft3d_ex: bad arguments");
+  FISDF_CHECK(mesh[0] >= 1 && mesh[1] >= 1 && mesh[2] >= 1, "fft3d_ex: bad mesh");
+  FISDF_CHECK((h_plane_base == nullptr) == (h_plane_ld == nullptr),
+              "fft3d_ex: the plane table is two arrays (base and ld) or none");
+  // the plane table lives in a device buffer of this call: freed after a stream sync
+  PlaneRef* planes = nullptr;
+  if (h_plane_base) {
+    std::vector<PlaneRef> h(mesh[0]);
+    for (int i0 = 0; i0 < mesh[0]; ++i0) h[i0] = PlaneRef{h_plane_base[i0], h_plane_ld[i0]};
+    FISDF_HIP(hipMalloc(&planes, sizeof(PlaneRef) * mesh[0]));
+    if (hipMemcpy(planes, h.data(), sizeof(PlaneRef) * mesh[0], hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(planes);
+      FISDF_CHECK(false, "fft3d_ex: plane table upload failed");
+    }
+  }
+  const int rc = fft3d(c->stream, (const cplx*)in, in_ld, rowidx, (cplx*)out, out_ld, rows, mesh[0],
+                       mesh[1], mesh[2], h_kd, weight, nullptr, planes, h_m, in_real != 0);
+  if (planes) {
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(planes);
+  }
+  if (rc == 0 && rows > 0 && h_path) *h_path = fft3d_route(mesh[0], mesh[1], mesh[2], h_m);
+  return rc;
+}
+
 int fisdf_coulg(fisdf_ctx* c, const int mesh[3], const double a[9], const double k[3],
                 double scale, int take_sqrt, double* w) {
   FISDF_TRY(device_guard(c));

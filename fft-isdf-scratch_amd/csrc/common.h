@@ -183,6 +183,12 @@ int fft3d(hipStream_t s, const cplx* in, long in_ld, const int* rowidx, cplx* ou
           int rows, int n0, int n1, int n2, const double* kd /*3 or null*/,
           const double* weight /*ngrid or null*/, cplx* work, const PlaneRef* planes = nullptr,
           const int* herm = nullptr, bool in_real = false);
+// the kernels fft3d runs for a mesh (herm as given to fft3d): register plane + axis-0 kernels,
+// the same with the Hermitian-paired axis-0 kernel, the LDS plane kernel + an axis-0 Stockham
+// pass, or three Stockham axis passes; | FFT_BIG when one of the Stockham passes is the
+// radix-7/11/13 instantiation
+enum FftRoute { FFT_REG = 0, FFT_REG_HERM = 1, FFT_PLANE = 2, FFT_AXES = 3, FFT_BIG = 16 };
+int fft3d_route(int n0, int n1, int n2, const int* herm);
 // whether fft3d takes sliced input for this mesh (its first pass is a per-plane kernel)
 bool fft3d_reads_slices(int n0, int n1, int n2);
 // whether fft3d takes real input (in_real: rows of doubles at the same strides) for this mesh

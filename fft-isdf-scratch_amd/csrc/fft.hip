@@ -560,7 +560,8 @@ __global__ __launch_bounds__(256) void fft_axis0_herm(const cplx* in, long in_ld
     __builtin_nontemporal_store(fft_dv2{x[p].x, x[p].y}, (fft_dv2*)(dst + (long)p * P));
 }
 
-// meshes with register kernels (cubic n^3 for the plane kernel; any n0 for axis 0)
+// sizes with register kernels: the plane kernel takes square n x n planes of a listed n, the
+// axis-0 kernels a listed n0 (n0 need not equal n: reg_mesh)
 #define FISDF_REG_SIZES(X) X(8) X(12) X(13) X(15) X(16) X(18) X(20) X(24) X(25) X(27) X(30) X(32) X(36) X(40) X(45) X(48)
 
 int fft_plane_reg_launch(hipStream_t s, int n, const cplx* in, long in_ld, const int* rowidx,
@@ -599,11 +600,15 @@ int fft_axis0_reg_launch(hipStream_t s, int n0, const cplx* in, long in_ld, cplx
   return 0;
 }
 
-int fft_axis0_herm_launch(hipStream_t s, int n0, const cplx* in, long in_ld, cplx* out,
-                          long out_ld, int rows, int n1, int n2, int n1H, const int m[3],
-                          const cplx* W, const double* weight, bool* done) {
-  *done = false;
-  auto partner1 = [&](int j) { return ((-j - m[1]) % n1 + n1) % n1; };
+// line pairing and grid of fft_axis0_herm, with its host-side checks (fft3d runs them before the
+// plane pass, so a refused call has written nothing)
+struct HermGeom {
+  int lo, hi, sl0, sl1;
+  long npb, blocks;
+};
+
+int herm_geom(int rows, int n1, int n2, int n1H, int m1, HermGeom* g) {
+  auto partner1 = [&](int j) { return ((-j - m1) % n1 + n1) % n1; };
   // stored lines: [lo, hi) pair with skipped lines; sl0 / sl1 are self-paired (or -1)
   const int sl0 = partner1(0) == 0 ? 0 : -1;
   const int sl1 = (n1H - 1 > 0 && partner1(n1H - 1) == n1H - 1) ? n1H - 1 : -1;
@@ -615,6 +620,18 @@ int fft_axis0_herm_launch(hipStream_t s, int n0, const cplx* in, long in_ld, cpl
   const long nself = (long)rows * ((sl0 >= 0) + (sl1 >= 0)) * n2;
   const long blocks = npb + (nself + 255) / 256;
   FISDF_CHECK(blocks < (1L << 31), "fft: too many blocks");
+  *g = HermGeom{lo, hi, sl0, sl1, npb, blocks};
+  return 0;
+}
+
+int fft_axis0_herm_launch(hipStream_t s, int n0, const cplx* in, long in_ld, cplx* out,
+                          long out_ld, int rows, int n1, int n2, int n1H, const int m[3],
+                          const cplx* W, const double* weight, bool* done) {
+  *done = false;
+  HermGeom hg;
+  FISDF_TRY(herm_geom(rows, n1, n2, n1H, m[1], &hg));
+  const int lo = hg.lo, hi = hg.hi, sl0 = hg.sl0, sl1 = hg.sl1;
+  const long npb = hg.npb, blocks = hg.blocks;
 #define FISDF_AXH(N)                                                                           \
   if (n0 == N) {                                                                               \
     if (m[0] == 0)                                                                             \
@@ -690,15 +707,21 @@ int largest_divisor_le(int x, int cap) {
   return 1;
 }
 
-int axis_pass(hipStream_t s, const cplx* in, long in_ld, const int* rowidx, cplx* out, long out_ld,
-              int rows, int axis, int n0, int n1, int n2, const double* kd, const double* weight) {
+// tiling of one fft_axis_kernel pass, with every host-side check of the pass (fft3d runs them for
+// all of its passes before it launches the first, so a refused call has written nothing)
+struct AxisGeom {
+  int n, inner, outer, contiguous, TL;
+  long tiles;
+  size_t lds;
+  Stages st;
+};
+
+int axis_geom(int rows, int axis, int n0, int n1, int n2, AxisGeom* g) {
   const int dims[3] = {n0, n1, n2};
   const int n = dims[axis];
-  Stages st;
+  FISDF_CHECK(n0 >= 1 && n1 >= 1 && n2 >= 1, "fft: mesh dimension must be in [1, 64]");
   FISDF_CHECK(n >= 1 && n <= MAXN, "fft: mesh dimension must be in [1, 64]");
-  FISDF_CHECK(factorize(n, st), "fft: mesh dimension must factor into 2,3,5,7,11,13");
-  const cplx* tw = nullptr;
-  FISDF_TRY(get_twiddles(n, &tw));
+  FISDF_CHECK(factorize(n, g->st), "fft: mesh dimension must factor into 2,3,5,7,11,13");
   int inner = 1, outer = 1;
   for (int a = axis + 1; a < 3; ++a) inner *= dims[a];
   for (int a = 0; a < axis; ++a) outer *= dims[a];
@@ -717,6 +740,21 @@ int axis_pass(hipStream_t s, const cplx* in, long in_ld, const int* rowidx, cplx
   FISDF_CHECK(tiles < (1L << 31), "fft: too many tiles");
   size_t lds = sizeof(cplx) * (MAXN + 2 * (size_t)TL * n);
   FISDF_CHECK(lds <= 160 * 1024, "fft: LDS tile too large");
+  g->n = n; g->inner = inner; g->outer = outer; g->contiguous = contiguous; g->TL = TL;
+  g->tiles = tiles; g->lds = lds;
+  return 0;
+}
+
+int axis_pass(hipStream_t s, const cplx* in, long in_ld, const int* rowidx, cplx* out, long out_ld,
+              int rows, int axis, int n0, int n1, int n2, const double* kd, const double* weight) {
+  AxisGeom g;
+  FISDF_TRY(axis_geom(rows, axis, n0, n1, n2, &g));
+  const int n = g.n, inner = g.inner, outer = g.outer, contiguous = g.contiguous, TL = g.TL;
+  const long tiles = g.tiles;
+  const size_t lds = g.lds;
+  const Stages& st = g.st;
+  const cplx* tw = nullptr;
+  FISDF_TRY(get_twiddles(n, &tw));
   double k0 = 0, k1 = 0, k2 = 0;
   int use_phase = kd != nullptr;
   if (kd) { k0 = kd[0]; k1 = kd[1]; k2 = kd[2]; }
@@ -761,6 +799,20 @@ bool fft_herm_enabled() {
   return on;
 }
 
+// which kernels fft3d runs for a mesh: the one place that decides it (fft3d branches on it, the
+// test entry fisdf_fft3d_ex reports it).  FFT_BIG is added when a pass of the Stockham routes
+// needs the radix-7/11/13 instantiation.
+int fft3d_route(int n0, int n1, int n2, const int* herm) {
+  if (reg_mesh(n0, n1, n2))
+    return herm && (herm[0] == 0 || herm[0] == 1) && fft_herm_enabled() ? FFT_REG_HERM : FFT_REG;
+  bool big = false;
+  for (int n : {n0, n1, n2}) {
+    Stages st;
+    if (n >= 1 && n <= MAXN && factorize(n, st)) big = big || needs_big(st);
+  }
+  return (plane_kernel_lds(n1, n2) <= 96 * 1024 ? FFT_PLANE : FFT_AXES) | (big ? FFT_BIG : 0);
+}
+
 int fft3d(hipStream_t s, const cplx* in, long in_ld, const int* rowidx, cplx* out, long out_ld,
           int rows, int n0, int n1, int n2, const double* kd, const double* weight, cplx* /*work*/,
           const PlaneRef* planes, const int* herm, bool in_real) {
@@ -769,17 +821,21 @@ int fft3d(hipStream_t s, const cplx* in, long in_ld, const int* rowidx, cplx* ou
               "fft: real input needs the register path and unsliced, out-of-place rows");
   FISDF_CHECK(in != out || rowidx == nullptr, "fft: in-place pass cannot gather rows");
   FISDF_CHECK(!planes || fft3d_reads_slices(n0, n1, n2), "fft: sliced input needs a plane kernel");
-  if (reg_mesh(n0, n1, n2)) {  // register kernels: square (i1, i2) planes of a listed size, listed n0
+  const int route = fft3d_route(n0, n1, n2, herm) & ~FFT_BIG;
+  if (route == FFT_REG || route == FFT_REG_HERM) {
+    // register kernels: square (i1, i2) planes of a listed size, listed n0
     const cplx *W12 = nullptr, *W0 = nullptr;
     FISDF_TRY(get_twiddles(n1, &W12));
     FISDF_TRY(get_twiddles(n0, &W0));
     bool ok1 = false, ok0 = false;
     FISDF_CHECK((long)rows * n0 < (1L << 31) && (long)rows * n1 * n2 < (1L << 38), "fft: too large");
-    if (herm && (herm[0] == 0 || herm[0] == 1) && fft_herm_enabled()) {
+    if (route == FFT_REG_HERM) {
       // Hermitian-paired input: the plane pass stores the lines j1 < n1H, the axis-0 pass
       // completes their partners and writes the prefix planes only
       const int m[3] = {herm[0], ((herm[1] % n1) + n1) % n1, ((herm[2] % n2) + n2) % n2};
       const int n1H = herm_prefix(n1, m[1]);
+      HermGeom hg;  // the axis-0 pass's checks, before the plane pass writes anything
+      FISDF_TRY(herm_geom(rows, n1, n2, n1H, m[1], &hg));
       FISDF_TRY(fft_plane_reg_launch(s, n1, in, in_ld, rowidx, out, out_ld, rows, n0, W12, kd,
                                      planes, n1H, in_real, &ok1));
       FISDF_TRY(fft_axis0_herm_launch(s, n0, out, out_ld, out, out_ld, rows, n1, n2, n1H, m, W0,
@@ -795,8 +851,13 @@ int fft3d(hipStream_t s, const cplx* in, long in_ld, const int* rowidx, cplx* ou
       return 0;
     }
   }
+  // every pass's host-side checks before the first launch: a mesh the last pass refuses (a
+  // dimension without a factorisation, an axis-0 tile beyond the LDS) leaves out untouched
+  AxisGeom geom;
+  for (int axis = route == FFT_PLANE ? 0 : 2; axis >= 0; --axis)
+    FISDF_TRY(axis_geom(rows, axis, n0, n1, n2, &geom));
   const size_t plane_lds = plane_kernel_lds(n1, n2);
-  if (plane_lds <= 96 * 1024) {
+  if (route == FFT_PLANE) {
     // axes 2+1 fused per (i1,i2) plane, then axis 0 with the Coulomb weight: 2 HBM passes
     Stages st1, st2;
     FISDF_CHECK(n1 <= MAXN && n2 <= MAXN && factorize(n1, st1) && factorize(n2, st2),

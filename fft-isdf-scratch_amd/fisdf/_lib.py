@@ -97,6 +97,8 @@ _SIGS = {
     "fisdf_herk": ([_vp, _i, _i, _d, _vp, _l, _vp, _l, _i], _i),
     "fisdf_fft3d": ([_vp, _vp, _vp, _i, _ip], _i),
     "fisdf_fft3d_paired": ([_vp, _vp, _vp, _i, _ip, _dp, _ip, _i], _i),
+    "fisdf_fft3d_ex": ([_vp, _vp, _l, _vp, _vp, _l, _i, _ip, _dp, _vp, C.POINTER(_l), C.POINTER(_l),
+                        _ip, _i, _ip], _i),
     "fisdf_coulg": ([_vp, _ip, _dp, _dp, _d, _i, _vp], _i),
     "fisdf_pivoted_cholesky": ([_vp, _vp, _i, _i, _i, _d, _ip, _ip], _i),
     "fisdf_cholesky": ([_vp, _vp, _i, _i, _d, _ip], _i),

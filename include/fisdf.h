@@ -538,6 +538,22 @@ int fisdf_fft3d(fisdf_ctx* ctx, const void* d_in, void* d_out, int rows, const i
  * register meshes only (an error otherwise) */
 int fisdf_fft3d_paired(fisdf_ctx* ctx, const void* d_in, void* d_out, int rows, const int mesh[3],
                        const double kd[3], const int m[3], int in_real);
+/* everything the library's FFT takes, for tests of its dispatch: rows of the input at stride in_ld
+ * (complex elements; doubles with in_real), d_rowidx (device, `rows` ints, or NULL) the input row
+ * each output row is gathered from, output rows at stride out_ld, h_kd (3, or NULL) the phase
+ * exp(-i f.kd) applied before the transform, d_weight (device, n0*n1*n2 doubles, or NULL)
+ * multiplied into the result, h_plane_base / h_plane_ld (n0 each, or both NULL) sliced input:
+ * plane i0 of input row r at d_in + h_plane_base[i0] + r * h_plane_ld[i0] (in_ld unused; the
+ * table is uploaded to a buffer of this call, which then waits for the stream before it frees
+ * it), h_m / in_real as fisdf_fft3d_paired.  d_in == d_out (equal strides, no gather) transforms
+ * in place.  *h_path (may be NULL) = the kernels that ran: 0 register kernels, 1 register kernels
+ * with Hermitian pairing, 2 LDS plane kernel + axis-0 pass, 3 three axis passes, + 16 when a
+ * pass ran as the radix-7/11/13 instantiation; -1 when nothing ran (rows = 0, or an error).  A
+ * call the library cannot do fails before it launches anything. */
+int fisdf_fft3d_ex(fisdf_ctx* ctx, const void* d_in, long in_ld, const int* d_rowidx, void* d_out,
+                   long out_ld, int rows, const int mesh[3], const double* h_kd,
+                   const double* d_weight, const long* h_plane_base, const long* h_plane_ld,
+                   const int* h_m, int in_real, int* h_path);
 /* sqrt(coulG(k+G) * scale) (or without sqrt), PySCF get_coulG(exxdiv=None) restated */
 int fisdf_coulg(fisdf_ctx* ctx, const int mesh[3], const double a[9], const double k[3],
                 double scale, int take_sqrt, double* d_w);
