@@ -1208,6 +1208,139 @@ int fisdf_tri_inverse(fisdf_ctx* c, const void* L, int n, int batch, void* Linv)
   return 0;
 }
 
+// ---- the factor-and-solve chain piece by piece, for tests of its dispatch (thin forwards) ----
+int fisdf_pivoted_cholesky_ex(fisdf_ctx* c, const void* A, long lda, long sA, int n, int batch,
+                              int rmax, double tol_rel, double tol_abs, void* Lf, int* d_piv,
+                              int* d_rank, int* h_path) {
+  FISDF_TRY(device_guard(c));
+  if (h_path) *h_path = -1;
+  FISDF_CHECK(A && Lf && d_piv && d_rank, "pivoted_cholesky_ex: null argument");
+  FISDF_CHECK(n >= 1 && batch >= 1 && rmax >= 1 && rmax <= n, "pivoted_cholesky_ex: bad sizes");
+  FISDF_CHECK(lda >= n && (batch == 1 || sA >= (long)(n - 1) * lda + n),
+              "pivoted_cholesky_ex: lda / batch stride smaller than the matrix");
+  Carver cv;
+  size_t oD = cv.take(sizeof(double) * (size_t)batch * n);
+  size_t oF = cv.take(sizeof(int) * batch);
+  size_t oW = cv.take(sizeof(double) * (size_t)batch * (1 + rmax));
+  void* base;
+  FISDF_TRY(arena_get(c, cv.off, &base));
+  char* b = (char*)base;
+  void* trail = nullptr;
+  FISDF_TRY(devbuf_get(c->ws_main, sizeof(cplx) * pchol_trail_elems(n, batch), &trail));
+  FISDF_TRY(pchol(c->stream, (const cplx*)A, lda, sA, n, batch, rmax, tol_rel, tol_abs, (cplx*)Lf,
+                  d_piv, d_rank, (double*)(b + oD), (int*)(b + oF), (double*)(b + oW),
+                  (cplx*)trail));
+  FISDF_HIP(hipStreamSynchronize(c->stream));
+  if (h_path) *h_path = pchol_path(n);
+  return 0;
+}
+
+int fisdf_gather_lp(fisdf_ctx* c, const void* Lf, int n, int rmax, const int* d_piv,
+                    const int* d_rank, int rpad, void* Lp, int batch) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(n >= 1 && rmax >= 1 && rmax <= n && rpad >= 0 && rpad <= rmax && batch >= 0,
+              "gather_lp: bad sizes");
+  FISDF_TRY(gather_lp(c->stream, (const cplx*)Lf, n, rmax, d_piv, d_rank, rpad, (cplx*)Lp, batch));
+  FISDF_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int fisdf_trsm_blocked_ex(fisdf_ctx* c, int lower, const void* Lp, long ldl, long sL, int r,
+                          void* B, long ldb, long sB, void* X, long ldx, long sX, int ncol,
+                          int batch, int a_real) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(r >= 1 && ncol >= 1 && batch >= 1 && ldl >= r && ldb >= ncol && ldx >= ncol,
+              "trsm_blocked_ex: bad sizes");
+  const int nb = 64, nblk = (r + nb - 1) / nb;  // the product's block (f_nb)
+  const long sLi = (long)nblk * nb * nb;
+  void* base;
+  FISDF_TRY(arena_get(c, sizeof(cplx) * (size_t)sLi * batch, &base));
+  // the diagonal-block inverses as factor_finish builds them
+  FISDF_TRY(trinv_blocks(c->stream, (const cplx*)Lp, r, (int)ldl, sL, nb, sLi, (cplx*)base, batch));
+  FISDF_TRY(trsm_blocked(c->stream, lower, (const cplx*)Lp, ldl, sL, r, (const cplx*)base, sLi, nb,
+                         (cplx*)B, ldb, sB, (cplx*)X, ldx, sX, ncol, batch, a_real));
+  FISDF_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int fisdf_trsm_merged_ex(fisdf_ctx* c, const void* Lp, long sL, int r, void* X, long ld, long sX,
+                         int ncol, int batch, int lower_rhs, int use_work, long work_elems,
+                         int* h_rows, int rows_cap) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(r >= 1 && ncol >= 1 && batch >= 1 && ld >= ncol && work_elems >= 0,
+              "trsm_merged_ex: bad sizes");
+  const int nblk = trsm_merged_blocks(r);
+  FISDF_CHECK(!h_rows || rows_cap >= nblk, "trsm_merged_ex: h_rows too short");
+  const long rr = (long)r * r;
+  Carver cv;
+  size_t oQ = cv.take(sizeof(cplx) * (size_t)batch * rr);
+  size_t oK = cv.take(sizeof(cplx) * (size_t)std::max(1L, work_elems));
+  void* base;
+  FISDF_TRY(arena_get(c, cv.off, &base));
+  cplx* Q = (cplx*)((char*)base + oQ);
+  cplx* work = use_work ? (cplx*)((char*)base + oK) : nullptr;
+  if (h_rows)
+    for (int b = 0; b < nblk; ++b) {
+      TrsmRow row;
+      trsm_merged_row(r, ncol, batch, lower_rhs != 0, use_work != 0, work_elems, b, &row);
+      const int v[6] = {row.b0, row.m, row.b1, row.nc, row.ks, row.sub};
+      std::memcpy(h_rows + 6 * b, v, sizeof(v));
+    }
+  FISDF_TRY(build_trsm_q(c->stream, (const cplx*)Lp, r, sL, Q, batch, GEMM_FULL));
+  const int rc = trsm_merged_batched(c->stream, Q, rr, r, (cplx*)X, ld, sX, ncol, batch,
+                                     lower_rhs != 0, work, use_work ? work_elems : 0);
+  FISDF_HIP(hipStreamSynchronize(c->stream));
+  return rc;
+}
+
+int fisdf_scatter_w(fisdf_ctx* c, const void* Wpp, int ldw, long sW, int rmax, const int* d_piv,
+                    const int* d_rank, void* W, int nip, int batch) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(nip >= 1 && rmax >= 0 && rmax <= nip && ldw >= rmax && batch >= 0,
+              "scatter_w: bad sizes");
+  FISDF_TRY(scatter_w(c->stream, (const cplx*)Wpp, ldw, sW, rmax, d_piv, d_rank, (cplx*)W, nip,
+                      batch));
+  FISDF_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int fisdf_conj_transpose(fisdf_ctx* c, const void* A, int n, long sA, void* B, int batch) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(n >= 1 && batch >= 0 && A != B, "conj_transpose: bad arguments");
+  FISDF_TRY(conj_transpose(c->stream, (const cplx*)A, n, sA, (cplx*)B, batch));
+  FISDF_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int fisdf_factor_plan(int n, int ncol, int batch, long work_elems, int* h_pchol_path,
+                      int* h_pchol_nb, int* h_nblk, int* h_s0, int* h_rows, int rows_cap,
+                      long* h_split_work_elems, int* h_sel_rpt, int* h_sel_nb) {
+  t_cur_ctx = nullptr;
+  FISDF_CHECK(n >= 1 && ncol >= 1 && batch >= 1, "factor_plan: bad sizes");
+  const int nblk = trsm_merged_blocks(n);
+  FISDF_CHECK(!h_rows || rows_cap >= nblk, "factor_plan: h_rows too short");
+  if (h_pchol_path) *h_pchol_path = pchol_path(n);
+  if (h_pchol_nb) *h_pchol_nb = PCHOL_NB;
+  if (h_nblk) *h_nblk = nblk;
+  TrsmRow row;
+  trsm_merged_row(n, ncol, batch, false, false, 0, 0, &row);
+  if (h_s0) *h_s0 = row.m;
+  if (h_rows)
+    for (int b = 0; b < nblk; ++b) {
+      TrsmRow full, low;
+      trsm_merged_row(n, ncol, batch, false, work_elems >= 0, work_elems, b, &full);
+      trsm_merged_row(n, ncol, batch, true, work_elems >= 0, work_elems, b, &low);
+      const int v[8] = {full.b0, full.m, full.b1, full.ks, full.sub, low.nc, low.ks, low.sub};
+      std::memcpy(h_rows + 8 * b, v, sizeof(v));
+    }
+  if (h_split_work_elems) *h_split_work_elems = trsm_split_work_elems(n, batch);
+  int rpt = 0, nb = 0;
+  pchol_real_variant(n, &rpt, &nb);
+  if (h_sel_rpt) *h_sel_rpt = rpt;
+  if (h_sel_nb) *h_sel_nb = nb;
+  return 0;
+}
+
 // ---- A1 ---------------------------------------------------------------------
 // The streamed y build's work on aux[2] and aux[0], enqueued right after the selection kernel (so
 // it never precedes it on any queue): the fused y kernel block by block, each block's XT rows

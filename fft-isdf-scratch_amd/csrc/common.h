@@ -137,6 +137,15 @@ int pchol(hipStream_t s, const cplx* A, long lda, long sA, int n, int batch, int
           int* rank /*batch, device*/, double* d /*batch,n*/, int* flags /*batch*/,
           double* work /*batch*(1+rmax)*/, cplx* trail);
 size_t pchol_trail_elems(int n, int batch);
+// the kernels pchol runs for an n x n matrix: panels of PCHOL_NB pivots held in registers by one
+// workgroup per matrix with ZGEMM trailing updates, or (n beyond one workgroup's rows) one
+// pchol_step + pchol_pick launch per pivot
+enum PcholPath { PCHOL_BLOCKED = 0, PCHOL_STEP = 1 };
+constexpr int PCHOL_NB = 32;
+int pchol_path(int n);
+// (rows per thread, pivots per panel) of the instantiation of the real selection panel kernel
+// that pchol_select_real's blocked path runs for n; false (0, 0) when n is beyond it
+bool pchol_real_variant(int n, int* rpt, int* nb);
 
 // unpivoted blocked Cholesky (full-rank fast path); see pchol.hip
 int chol_unpivoted(hipStream_t s, cplx* W, int n, int batch, double tol_rel, int* piv, int* rank,

@@ -22,6 +22,16 @@ int trsm_merged_batched(hipStream_t s, const cplx* Q, long sQ, int r, cplx* X, l
 // (complex elements) that lets a batch of `batch` r x r matrices run in one launch per row
 int trsm_split_k(int nc, int b1);
 long trsm_split_work_elems(int r, int batch);
+// the partition of trsm_merged_batched (the partial block first) and what it does per block row
+struct TrsmRow {
+  int b0, m, b1;  // rows [b0, b0 + m), K = b1 = b0 + m
+  int nc;         // columns computed
+  int ks;         // split-K
+  int sub;        // matrices per launch (sub-batches when the workspace is short)
+};
+int trsm_merged_blocks(int r);
+bool trsm_merged_row(int r, int ncol, int batch, bool lower_rhs, bool have_work, long work_elems,
+                     int b, TrsmRow* row);
 int set_identity(hipStream_t s, cplx* X, int n, int batch);
 // out[g][j*nao + m] = h_sc[j] * x0[h_k[j]][g][m] for the nsel listed k (any nsel)
 int permute_kgm_sel(hipStream_t s, const cplx* x0, const int* h_k, const double* h_sc, int nsel,

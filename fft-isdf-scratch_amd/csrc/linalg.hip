@@ -1004,25 +1004,50 @@ long trsm_split_work_elems(int r, int batch) {
   return mx * batch;
 }
 
+int trsm_merged_blocks(int r) { return (r + 63) / 64; }
+
+// block row b of the merged substitution and how trsm_merged_batched runs it: rows [b0, b0 + m),
+// K = b1 = b0 + m, nc columns (a lower-triangular right-hand side has none beyond b1), split-K ks
+// (1 without a workspace) and the matrices per launch sub; false if the workspace cannot hold one
+// matrix's partials
+bool trsm_merged_row(int r, int ncol, int batch, bool lower_rhs, bool have_work, long work_elems,
+                     int b, TrsmRow* row) {
+  const int nblk = trsm_merged_blocks(r), s0 = r - 64 * (nblk - 1);
+  row->b0 = b == 0 ? 0 : s0 + (b - 1) * 64;
+  row->m = std::min(b == 0 ? s0 : 64, r - row->b0);
+  row->b1 = row->b0 + row->m;
+  row->nc = lower_rhs ? std::min(ncol, row->b1) : ncol;
+  row->ks = have_work ? trsm_split_k(row->nc, row->b1) : 1;
+  const long per = (long)row->ks * row->m * row->nc;  // partials of one matrix
+  row->sub = batch;
+  if (row->ks > 1) {
+    if (per > work_elems) {
+      row->sub = 0;
+      return false;
+    }
+    row->sub = (int)std::max(1L, std::min<long>(batch, work_elems / per));
+  }
+  return true;
+}
+
 int trsm_merged_batched(hipStream_t s, const cplx* Q, long sQ, int r, cplx* X, long ld, long sX,
                         int ncol, int batch, bool lower_rhs, cplx* work, long work_elems) {
-  const int nblk = (r + 63) / 64;
+  const int nblk = trsm_merged_blocks(r);
   if (nblk == 0 || batch == 0) return 0;
-  const int s0 = r - 64 * (nblk - 1);
   const cplx one = cmk(1, 0), zero = cmk(0, 0);
+  TrsmRow row;
+  // every block row's workspace need is checked before the first launch: the update is in place,
+  // so a failure after a launch would leave X half overwritten
+  for (int b = 0; b < nblk; ++b)
+    FISDF_CHECK(trsm_merged_row(r, ncol, batch, lower_rhs, work != nullptr, work_elems, b, &row),
+                "trsm_merged_batched: split-K workspace too small");
   for (int b = 0; b < nblk; ++b) {
-    const int b0 = b == 0 ? 0 : s0 + (b - 1) * 64;
-    const int m = std::min(b == 0 ? s0 : 64, r - b0), b1 = b0 + m;
-    const int nc = lower_rhs ? std::min(ncol, b1) : ncol;
-    const int ks = work ? trsm_split_k(nc, b1) : 1;
-    const long per = (long)ks * m * nc;  // partials of one matrix
-    const int sub = ks > 1 ? (int)std::max(1L, std::min<long>(batch, work_elems / per)) : batch;
-    FISDF_CHECK(ks == 1 || per <= work_elems, "trsm_merged_batched: split-K workspace too small");
-    for (int z0 = 0; z0 < batch; z0 += sub) {
-      const int nb = std::min(sub, batch - z0);
-      FISDF_TRY(zgemm(s, OP_N, OP_N, m, nc, b1, one, Q + z0 * sQ + (long)b0 * r, r, sQ,
-                      X + z0 * sX, ld, sX, zero, X + z0 * sX + (long)b0 * ld, ld, sX, nb, ks,
-                      ks > 1 ? work : nullptr));
+    trsm_merged_row(r, ncol, batch, lower_rhs, work != nullptr, work_elems, b, &row);
+    for (int z0 = 0; z0 < batch; z0 += row.sub) {
+      const int nb = std::min(row.sub, batch - z0);
+      FISDF_TRY(zgemm(s, OP_N, OP_N, row.m, row.nc, row.b1, one, Q + z0 * sQ + (long)row.b0 * r, r,
+                      sQ, X + z0 * sX, ld, sX, zero, X + z0 * sX + (long)row.b0 * ld, ld, sX, nb,
+                      row.ks, row.ks > 1 ? work : nullptr));
     }
   }
   return 0;

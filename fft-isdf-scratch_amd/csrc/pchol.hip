@@ -1363,31 +1363,37 @@ __global__ void chol_finish_kernel(int n, int* __restrict__ piv, int* __restrict
 }  // namespace
 
 // pivot values are kept in `dmax0 + batch` (caller allocates 2*batch + batch*rmax doubles: see api)
-size_t pchol_trail_elems(int n, int batch) { return n <= PB_THREADS ? (size_t)n * n * batch : 0; }
+int pchol_path(int n) { return n <= PB_THREADS ? PCHOL_BLOCKED : PCHOL_STEP; }
+
+size_t pchol_trail_elems(int n, int batch) {
+  return pchol_path(n) == PCHOL_BLOCKED ? (size_t)n * n * batch : 0;
+}
 
 int pchol(hipStream_t s, const cplx* A, long lda, long sA, int n, int batch, int rmax,
           double tol_rel, double tol_abs, cplx* L, int* piv, int* rank, double* d, int* flags,
           double* work, cplx* trail) {
   FISDF_CHECK(n > 0 && batch > 0 && rmax > 0 && rmax <= n, "pchol: bad sizes");
   FISDF_CHECK(batch < 65536, "pchol: batch too large");
+  const int path = pchol_path(n);
+  FISDF_CHECK(path != PCHOL_BLOCKED || trail != nullptr, "pchol: trailing-update workspace missing");
   double* thr = work;                  // batch
   double* pval = work + batch;         // batch * rmax
   const int nt = 1024;
   hipLaunchKernelGGL(pchol_init, dim3(batch), dim3(nt), 0, s, A, lda, sA, n, rmax, tol_rel,
                      tol_abs, piv, pval, rank, d, flags, thr);
   FISDF_HIP(hipGetLastError());
-  if (n <= PB_THREADS) {
+  if (path == PCHOL_BLOCKED) {
     // blocked: trailing copy W of A, panels of NB pivots, batched ZGEMM trailing updates
-    constexpr int NB = 32;
+    constexpr int NB = PCHOL_NB;
     const long nn = (long)n * n;
     cplx* W = trail;  // the caller's (pchol_trail_elems): no stream-ordered pool memory
-    FISDF_CHECK(W != nullptr, "pchol: trailing-update workspace missing");
-    FISDF_HIP(hipMemcpy2DAsync(W, sizeof(cplx) * n, A, sizeof(cplx) * lda, sizeof(cplx) * n,
-                               (size_t)n * batch, hipMemcpyDeviceToDevice, s));
     if (sA != (long)n * lda) {  // batch stride differs from a packed copy: copy per matrix
       for (int bb = 0; bb < batch; ++bb)
         FISDF_HIP(hipMemcpy2DAsync(W + bb * nn, sizeof(cplx) * n, A + bb * sA, sizeof(cplx) * lda,
                                    sizeof(cplx) * n, n, hipMemcpyDeviceToDevice, s));
+    } else {
+      FISDF_HIP(hipMemcpy2DAsync(W, sizeof(cplx) * n, A, sizeof(cplx) * lda, sizeof(cplx) * n,
+                                 (size_t)n * batch, hipMemcpyDeviceToDevice, s));
     }
     const cplx mone = cmk(-1, 0), one = cmk(1, 0);
     for (int j0 = 0; j0 < rmax; j0 += NB) {
@@ -1711,6 +1717,22 @@ int pchol_select_batch_launch(hipStream_t s, const cplx* X2, double scale, int n
   return 0;
 }
 
+// rows per thread and pivots per panel of the real selection panel kernel for an n x n Gram (512
+// threads hold RPT rows each; the panel shrinks as the rows' registers grow); false: n is beyond
+// the register panel (the caller then uses pchol)
+bool pchol_real_variant(int n, int* rpt, int* nb) {
+  const int per = (n + PR_THREADS - 1) / PR_THREADS;
+  int r = 0, b = 0;
+  if (n < 1 || per > 8) { r = 0; b = 0; }
+  else if (per <= 2) { r = 2; b = 16; }
+  else if (per <= 4) { r = 4; b = 16; }
+  else if (per <= 7) { r = 7; b = 12; }
+  else { r = 8; b = 8; }
+  if (rpt) *rpt = r;
+  if (nb) *nb = b;
+  return r != 0;
+}
+
 int pchol_select_real(hipStream_t s, const cplx* X2, double scale, int n, int rmax, double tol,
                       int* piv, int* rank, double* work, int* flags, bool* handled,
                       bool allow_coop, const int** coop_err, int* progress, bool* publishes) {
@@ -1732,7 +1754,7 @@ int pchol_select_real(hipStream_t s, const cplx* X2, double scale, int n, int rm
       return 0;
     }
   }
-  if (n > 8 * PR_THREADS) return 0;
+  if (!pchol_real_variant(n, nullptr, nullptr)) return 0;
   double* W = work;
   double* Lpan = W + (long)n * n;
   double* d = Lpan + (long)n * 16;
@@ -1743,14 +1765,16 @@ int pchol_select_real(hipStream_t s, const cplx* X2, double scale, int n, int rm
   hipLaunchKernelGGL(real_square_scale_kernel, dim3((unsigned)std::min<long>((n2 + 255) / 256, 8192)),
                      dim3(256), 0, s, X2, scale, W, d, n2, n);
   FISDF_HIP(hipGetLastError());
-  const int rpt = (n + PR_THREADS - 1) / PR_THREADS;
+  int rpt = 0, pnb = 0;
+  pchol_real_variant(n, &rpt, &pnb);
   const int nt = (n + 63) / 64;
   const dim3 ug(nt * (nt + 1) / 2);
 #define FISDF_PR(R, NBv)                                                                         for (int j0 = 0; j0 < rmax; j0 += NBv) {                                                          hipLaunchKernelGGL((pchol_real_panel<R, NBv>), dim3(1), dim3(PR_THREADS), 0, s, W, n, rmax,                        j0, tol, Lpan, piv, rank, d, flags, thr);                                   if (j0 + NBv < rmax)                                                                             hipLaunchKernelGGL((syrk_real_update<NBv>), ug, dim3(256), 0, s, W, n, Lpan, flags);        }
-  if (rpt <= 2) { FISDF_PR(2, 16) }
-  else if (rpt <= 4) { FISDF_PR(4, 16) }
-  else if (rpt <= 7) { FISDF_PR(7, 12) }
-  else { FISDF_PR(8, 8) }
+  if (rpt == 2 && pnb == 16) { FISDF_PR(2, 16) }
+  else if (rpt == 4 && pnb == 16) { FISDF_PR(4, 16) }
+  else if (rpt == 7 && pnb == 12) { FISDF_PR(7, 12) }
+  else if (rpt == 8 && pnb == 8) { FISDF_PR(8, 8) }
+  else FISDF_CHECK(false, "pchol_select_real: no panel kernel for this variant");
 #undef FISDF_PR
   FISDF_HIP(hipGetLastError());
   *handled = true;

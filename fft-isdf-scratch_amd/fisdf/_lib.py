@@ -103,6 +103,14 @@ _SIGS = {
     "fisdf_pivoted_cholesky": ([_vp, _vp, _i, _i, _i, _d, _ip, _ip], _i),
     "fisdf_cholesky": ([_vp, _vp, _i, _i, _d, _ip], _i),
     "fisdf_tri_inverse": ([_vp, _vp, _i, _i, _vp], _i),
+    "fisdf_pivoted_cholesky_ex": ([_vp, _vp, _l, _l, _i, _i, _i, _d, _d, _vp, _vp, _vp, _ip], _i),
+    "fisdf_gather_lp": ([_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i], _i),
+    "fisdf_trsm_blocked_ex": ([_vp, _i, _vp, _l, _l, _i, _vp, _l, _l, _vp, _l, _l, _i, _i, _i], _i),
+    "fisdf_trsm_merged_ex": ([_vp, _vp, _l, _i, _vp, _l, _l, _i, _i, _i, _i, _l, _ip, _i], _i),
+    "fisdf_scatter_w": ([_vp, _vp, _i, _l, _i, _vp, _vp, _vp, _i, _i], _i),
+    "fisdf_conj_transpose": ([_vp, _vp, _i, _l, _vp, _i], _i),
+    "fisdf_factor_plan": ([_i, _i, _i, _l, _ip, _ip, _ip, _ip, _ip, _i, C.POINTER(_l), _ip, _ip],
+                          _i),
     # composite entries
     "fisdf_build_opts_default": ([_vp], None),
     "fisdf_build": ([_vp, _vp, _i, _vp, _i, _ip, _ip, _dp, _vp, _ip], _i),

@@ -576,6 +576,60 @@ int fisdf_cholesky(fisdf_ctx* ctx, void* d_A, int n, int batch, double tol_rel, 
  * batch it is computed in */
 int fisdf_tri_inverse(fisdf_ctx* ctx, const void* d_L, int n, int batch, void* d_Linv);
 
+/* ---- the factor-and-solve chain piece by piece, for tests of its dispatch.  Every pointer named
+ * d_ is device memory, every call is synchronous and fails before it launches anything when it
+ * cannot run. ---- */
+/* everything the pivoted Cholesky takes: batch Hermitian PSD n x n matrices at d_A (row stride
+ * lda, batch stride sA >= n*lda, complex elements), at most rmax pivots per matrix, stop when the
+ * largest residual diagonal is not above max(tol_rel > 0 ? tol_rel * m : n * eps * m, tol_abs),
+ * m = max diag.  d_L (batch, n, rmax): column j = the factor's column of pivot j, rows in the
+ * matrix's own order; columns >= rank unspecified.  d_piv (batch, rmax): entries >= rank are left
+ * as they were.  d_rank (batch).  *h_path (may be NULL): 0 = panels of 32 pivots in one
+ * workgroup's registers (n <= 1024), 1 = one step per pivot */
+int fisdf_pivoted_cholesky_ex(fisdf_ctx* ctx, const void* d_A, long lda, long sA, int n, int batch,
+                              int rmax, double tol_rel, double tol_abs, void* d_L, int* d_piv,
+                              int* d_rank, int* h_path);
+/* d_Lp[b] (rpad x rpad, rpad <= rmax) = the rows of d_L[b] (n x rmax) in pivot order, lower
+ * triangle of the leading rank[b] x rank[b] block, the identity beyond the rank, zero elsewhere */
+int fisdf_gather_lp(fisdf_ctx* ctx, const void* d_L, int n, int rmax, const int* d_piv,
+                    const int* d_rank, int rpad, void* d_Lp, int batch);
+/* X = L^{-1} B (lower = 1) or L^{-H} B (lower = 0) by the fit's blocked substitution (64-row
+ * blocks, the diagonal-block inverses built here as the factor stage does).  L: the leading r x r
+ * of d_Lp (row stride ldl, batch stride sL); d_B (r x ncol, ldb, sB) is overwritten; d_X (ldx,
+ * sX).  a_real: Im L is taken as zero */
+int fisdf_trsm_blocked_ex(fisdf_ctx* ctx, int lower, const void* d_Lp, long ldl, long sL, int r,
+                          void* d_B, long ldb, long sB, void* d_X, long ldx, long sX, int ncol,
+                          int batch, int a_real);
+/* X <- L^{-1} X in place by the factor stage's merged block-row substitution: the block-row
+ * operator of d_Lp (batch of r x r, row stride r, batch stride sL) is built, then applied to d_X
+ * (r x ncol, row stride ld, batch stride sX).  lower_rhs: X is lower triangular (block row b is
+ * computed for its columns < b1 only).  use_work: split-K with a workspace of work_elems complex
+ * elements (batches that do not fit run in sub-batches; fewer than one matrix's partials is an
+ * error and leaves d_X as it was).  h_rows (may be NULL; rows_cap >= (r + 63) / 64 rows of 6
+ * ints): per block row b0, m, b1, columns, split-K, matrices per launch */
+int fisdf_trsm_merged_ex(fisdf_ctx* ctx, const void* d_Lp, long sL, int r, void* d_X, long ld,
+                         long sX, int ncol, int batch, int lower_rhs, int use_work,
+                         long work_elems, int* h_rows, int rows_cap);
+/* d_W[b] (nip x nip) = 0, then d_W[b][piv[s]][piv[t]] = d_Wpp[b][s][t] (row stride ldw, batch
+ * stride sW) for s, t < rank[b] <= rmax; d_piv rows are nip apart (the factor stage's layout) */
+int fisdf_scatter_w(fisdf_ctx* ctx, const void* d_Wpp, int ldw, long sW, int rmax,
+                    const int* d_piv, const int* d_rank, void* d_W, int nip, int batch);
+/* d_B[b] = d_A[b]^H for batch n x n matrices (row stride n, batch stride sA for both) */
+int fisdf_conj_transpose(fisdf_ctx* ctx, const void* d_A, int n, long sA, void* d_B, int batch);
+/* what the chain does for given sizes, from the host functions its launchers use (no context, no
+ * device): the pivoted Cholesky's path and panel width for an n x n matrix; the merged
+ * substitution's partition of n rows (h_nblk block rows, the first of *h_s0 rows) and, per block
+ * row, 8 ints in h_rows (rows_cap rows; may be NULL): b0, m, b1, then split-K and matrices per
+ * launch for a full right-hand side of ncol columns, then columns, split-K and matrices per launch
+ * for a lower-triangular one, all for a batch of `batch` with a workspace of work_elems complex
+ * elements (< 0: none; matrices per launch 0 = the workspace is too small); the workspace that
+ * lets the whole batch run in one launch per row with n columns; the (rows per thread, pivots per
+ * panel) of the real selection panel kernel for an n x n Gram (0, 0 beyond n = 4096).  Any output
+ * may be NULL */
+int fisdf_factor_plan(int n, int ncol, int batch, long work_elems, int* h_pchol_path,
+                      int* h_pchol_nb, int* h_nblk, int* h_s0, int* h_rows, int rows_cap,
+                      long* h_split_work_elems, int* h_sel_rpt, int* h_sel_nb);
+
 #ifdef __cplusplus
 }
 #endif
