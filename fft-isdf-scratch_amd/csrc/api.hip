@@ -3202,6 +3202,126 @@ int fisdf_get_j(fisdf_ctx* c, const void* Xv, const void* W0, const void* dmsv, 
   return fisdf_get_j_rows(c, Xv, W0, dmsv, nset, nk, nip, nao, 0, nip, vjv);
 }
 
+// ---- exact FFT-grid J (PySCF fft_jk.get_j_kpts; the kernels are in jfft.hip) ------------------
+}  // extern "C"
+
+namespace {
+
+// the host-side checks of a potential on `mesh` other than the FFT's own (fft3d makes those
+// when it is reached; until then only scratch is written)
+int potential_check(const int mesh[3], const double a[9], int nset, long* ngrid) {
+  FISDF_CHECK(mesh && a, "coulomb_potential: null mesh or lattice");
+  FISDF_CHECK(nset >= 1, "coulomb_potential: nset must be >= 1");
+  FISDF_CHECK(mesh[0] >= 1 && mesh[1] >= 1 && mesh[2] >= 1, "coulomb_potential: bad mesh");
+  FISDF_CHECK(cell_volume(a) > 0, "coulomb_potential: singular lattice");
+  *ngrid = (long)mesh[0] * mesh[1] * mesh[2];
+  FISDF_CHECK(*ngrid < (1L << 31), "coulomb_potential: mesh too large");
+  return 0;
+}
+
+// v_s = ifft(coulG(k = 0, omega) fft(rho_s)) with the forward fft3d only: t = fft(rho) coulG / N
+// (the weight of the transform's last pass), then v = conj(fft(conj(t))).  w (ngrid doubles) and
+// t (nset * ngrid) are scratch.  final_conj = false leaves conj(v) in v (weighted_gram's conj_v
+// takes it from there).  fft3d runs all its checks before its first launch, and nothing before it
+// writes v: a refused mesh leaves v untouched.
+int potential_enqueue(fisdf_ctx* c, const cplx* rho, int nset, const int mesh[3],
+                      const double a[9], double omega, double* w, cplx* t, cplx* v,
+                      bool final_conj) {
+  const long ngrid = (long)mesh[0] * mesh[1] * mesh[2];
+  CellGeom g;
+  lattice(a, g);
+  const double k0[3] = {0, 0, 0};
+  FISDF_TRY(coulg_weight(c->stream, mesh, g, k0, 1.0 / ngrid, 0, w, omega));
+  FISDF_TRY(fft3d(c->stream, rho, ngrid, nullptr, t, ngrid, nset, mesh[0], mesh[1], mesh[2],
+                  nullptr, w, nullptr));
+  FISDF_TRY(conj_inplace(c->stream, t, nset * ngrid));
+  FISDF_TRY(fft3d(c->stream, t, ngrid, nullptr, v, ngrid, nset, mesh[0], mesh[1], mesh[2], nullptr,
+                  nullptr, nullptr));
+  if (final_conj) FISDF_TRY(conj_inplace(c->stream, v, nset * ngrid));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fisdf_get_rho(fisdf_ctx* c, const void* fv, long f_kstride, int nk, int ngrid, int nao,
+                  const void* dmsv, int nset, void* rhov) {
+  FISDF_TRY(device_guard(c));
+  StageTimer tm(c, FISDF_ST_J);
+  return rho_grid(c->stream, (const cplx*)fv, f_kstride, nk, ngrid, nao, (const cplx*)dmsv, nset,
+                  (cplx*)rhov);
+}
+
+int fisdf_coulomb_potential(fisdf_ctx* c, const void* rhov, int nset, const int mesh[3],
+                            const double a[9], double omega, void* vv) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(rhov && vv, "coulomb_potential: null pointer");
+  long ngrid = 0;
+  FISDF_TRY(potential_check(mesh, a, nset, &ngrid));
+  StageTimer tm(c, FISDF_ST_J);
+  Carver cv;
+  size_t oW = cv.take(sizeof(double) * ngrid);
+  size_t oT = cv.take(sizeof(cplx) * nset * ngrid);
+  void* base;
+  FISDF_TRY(arena_get(c, cv.off, &base));
+  return potential_enqueue(c, (const cplx*)rhov, nset, mesh, a, omega,
+                           (double*)((char*)base + oW), (cplx*)((char*)base + oT), (cplx*)vv, true);
+}
+
+int fisdf_weighted_gram(fisdf_ctx* c, const void* fv, long f_kstride, int nk, int ngrid, int nao,
+                        const void* vv, int nset, int conj_v, double scale, void* outv) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(nk >= 1 && ngrid >= 1 && nao >= 1 && nset >= 1,
+              "weighted_gram: sizes must be >= 1");
+  StageTimer tm(c, FISDF_ST_J);
+  const long we = weighted_gram_work_elems(nk, ngrid, nao, nset);
+  void* base;
+  FISDF_TRY(arena_get(c, sizeof(cplx) * we, &base));
+  return weighted_gram(c->stream, (const cplx*)fv, f_kstride, nk, ngrid, nao, (const cplx*)vv,
+                       nset, conj_v, scale, (cplx*)outv, (cplx*)base, we);
+}
+
+int fisdf_get_j_fft(fisdf_ctx* c, const void* fv, long f_kstride, const int kmesh[3],
+                    const int mesh[3], const double a[9], int nao, const void* dmsv, int nset,
+                    double omega, const void* fbandv, int nband, void* vjv) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(fv && dmsv && vjv && kmesh, "get_j_fft: null pointer");
+  FISDF_CHECK(kmesh[0] >= 1 && kmesh[1] >= 1 && kmesh[2] >= 1, "get_j_fft: bad k-mesh");
+  FISDF_CHECK(nao >= 1, "get_j_fft: nao must be >= 1");
+  FISDF_CHECK(fbandv == nullptr || nband >= 1, "get_j_fft: band AOs without band k-points");
+  long ngl = 0;
+  FISDF_TRY(potential_check(mesh, a, nset, &ngl));
+  const long nkl = (long)kmesh[0] * kmesh[1] * kmesh[2];
+  FISDF_CHECK(nkl <= 65535, "get_j_fft: more than 65535 k-points");
+  FISDF_CHECK(f_kstride >= ngl * nao, "get_j_fft: f_kstride below ngrid * nao");
+  const int nk = (int)nkl, ngrid = (int)ngl;
+  // J at the k-mesh from f itself, or at the band k-points from their AOs on the same grid
+  const cplx* fo = fbandv ? (const cplx*)fbandv : (const cplx*)fv;
+  const long fo_ks = fbandv ? ngl * nao : f_kstride;
+  const int no = fbandv ? nband : nk;
+  StageTimer tm(c, FISDF_ST_J);
+  const long we = weighted_gram_work_elems(no, ngrid, nao, nset);
+  Carver cv;
+  size_t oW = cv.take(sizeof(double) * ngl);
+  size_t oR = cv.take(sizeof(cplx) * nset * ngl);
+  size_t oT = cv.take(sizeof(cplx) * nset * ngl);
+  size_t oV = cv.take(sizeof(cplx) * nset * ngl);
+  size_t oP = cv.take(sizeof(cplx) * we);
+  void* base;
+  FISDF_TRY(arena_get(c, cv.off, &base));
+  double* w = (double*)((char*)base + oW);
+  cplx* rho = (cplx*)((char*)base + oR);
+  cplx* t = (cplx*)((char*)base + oT);
+  cplx* v = (cplx*)((char*)base + oV);
+  FISDF_TRY(rho_grid(c->stream, (const cplx*)fv, f_kstride, nk, ngrid, nao, (const cplx*)dmsv,
+                     nset, rho));
+  // conj(v) is left in v: the Gram reads it conjugated
+  FISDF_TRY(potential_enqueue(c, rho, nset, mesh, a, omega, w, t, v, false));
+  return weighted_gram(c->stream, fo, fo_ks, no, ngrid, nao, v, nset, 1,
+                       cell_volume(a) / (double)ngl, (cplx*)vjv, (cplx*)((char*)base + oP), we);
+}
+
 // ---- A8 -----------------------------------------------------------------------
 static int get_k_block(fisdf_ctx* c, const void* Xv, const double* Ws_rows, long ws_Rstride,
                        const void* dmsv, int nset, int nip, int nao, const int kmesh[3],

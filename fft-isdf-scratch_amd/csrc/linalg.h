@@ -143,4 +143,24 @@ bool kmesh_y_reg_applies(const int kmesh[3], long ncol);
 int k_wsrho_reg(hipStream_t s, cplx* B, long ncol, const int kmesh[3], const double* Ws,
                 long ws_Rstride, unsigned long long* mon, bool* handled);
 
+// ---- exact FFT-grid J (jfft.hip; PySCF fft_jk.get_j_kpts) ----
+// both kernels take at most kJfftSetChunk sets per pass over f (one launch per chunk)
+constexpr int kJfftSetChunk = 4;
+// rho[s][g] = (1/nk) sum_k sum_mn f_k[g,m] D[s][k][m,n] conj(f_k[g,n]); f (nk, ngrid, nao) with k
+// stride fks; no workspace.  rho_grid_tiled: D_sk is staged in 32 x 32 tiles (nao > 32)
+int rho_grid(hipStream_t s, const cplx* f, long fks, int nk, int ngrid, int nao, const cplx* D,
+             int nset, cplx* rho);
+bool rho_grid_tiled(int nao);
+// out[s][k][m][n] = scale sum_g conj(f_k[g,m]) v_s[g] f_k[g,n] (conj_v: conj(v_s[g])), the grid
+// split into *nsplit runs of *chunk points (weighted_gram_split, from the shape only) whose
+// partial blocks are summed in split order; work: weighted_gram_work_elems complex elements
+constexpr long kGramWgs = 1024;
+void weighted_gram_split(int nk, int ngrid, int nao, int* chunk, int* nsplit);
+long weighted_gram_work_elems(int nk, int ngrid, int nao, int nset);
+int weighted_gram(hipStream_t s, const cplx* f, long fks, int nk, int ngrid, int nao,
+                  const cplx* v, int nset, int conj_v, double scale, cplx* out, cplx* work,
+                  long work_elems);
+// a[e] = conj(a[e]): ifft(x) = conj(fft(conj(x))) / N around the forward fft3d
+int conj_inplace(hipStream_t s, cplx* a, long n);
+
 }  // namespace fisdf

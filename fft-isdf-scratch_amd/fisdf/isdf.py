@@ -163,6 +163,12 @@ class InterpolativeSeparableDensityFitting:
     # all-to-all, the W_s all-reduce and W_0 broadcast, the get_jk all-reduces — how the RCCL path
     # is exercised on a single GPU (tests/test_gpu_rccl.py); needs ``comm``
     force_sharded = False
+    # where J comes from: "isdf" = the fit's W_0 (the reference, fftisdf.py:133-171); "fft" = the
+    # exact FFT-grid J (PySCF fft_jk.get_j_kpts: the density on the FFT grid, one forward and one
+    # inverse FFT, one weighted AO Gram over the resident Bloch AOs) — no fitting error, and
+    # defined at any band k-point.  K is the ISDF K either way.
+    j_method = "isdf"
+    J_METHODS = ("isdf", "fft")
 
     def __init__(self, cell, kpts, m0=None, c0=20.0, device=None, comm=None):
         self.cell = cell
@@ -375,17 +381,28 @@ class InterpolativeSeparableDensityFitting:
     def get_jk(self, dm, hermi=1, kpts=None, kpts_band=None, with_j=True, with_k=True,
                omega=None, exxdiv=None):
         """fftisdf.py:390-408."""
+        _check_j_method(self)
         if omega is not None and omega != 0:
             # range-separated kernel (PySCF get_coulG omega; the reference raises, :392-393):
             # W_q refitted once per omega with the attenuated weight, X and the AO inputs shared
             if exxdiv is not None:
                 raise NotImplementedError("exxdiv with a range-separated kernel")
-            return self._omega_df(float(omega)).get_jk(dm, hermi, kpts, kpts_band, with_j,
-                                                       with_k, None, None)
+            if self.j_method == "fft" and not with_k:
+                # the grid J takes omega as an argument: no refit of W_q for it
+                return self._get_jk(dm, kpts, kpts_band, with_j, False, None, float(omega))
+            sub = self._omega_df(float(omega))
+            sub.j_method = self.j_method     # the cached sub-object follows the parent's setting
+            return sub._get_jk(dm, kpts, kpts_band, with_j, with_k, None, float(omega))
         if exxdiv is not None and exxdiv != "ewald":
             # the reference raises for every exxdiv (:395-396); 'ewald' is added here as
             # PySCF's FFTDF does it (SURVEY.md §8f next-4): K + madelung * S_k D_k S_k
             raise NotImplementedError
+        return self._get_jk(dm, kpts, kpts_band, with_j, with_k, exxdiv,
+                            float(getattr(self, "_fit_omega", 0.0)))
+
+    def _get_jk(self, dm, kpts, kpts_band, with_j, with_k, exxdiv, j_omega):
+        """get_jk on this object's fitted state; j_omega: the range-separation parameter of the
+        grid J (j_method = "fft"), which takes it as an argument rather than from the fit."""
         kpts = self.kpts if kpts is None else np.asarray(kpts)
         if kpts.ndim == 1:                                            # _check_kpts single kpt
             raise NotImplementedError
@@ -397,7 +414,7 @@ class InterpolativeSeparableDensityFitting:
         if with_k:
             vk = _get_k_dev(self, ddms, exxdiv, band)
         if with_j:
-            vj = _get_j_dev(self, ddms, band)
+            vj = _get_j_dev(self, ddms, band, j_omega)
         if vk is not None and vj is not None and vk.shape == vj.shape:
             # one device-to-host copy (and one synchronisation) for both
             vk, vj = self.device.to_host(self.device.torch.stack((vk, vj)))
@@ -452,6 +469,39 @@ class InterpolativeSeparableDensityFitting:
         if st is not None:
             st["S"] = S
         return S
+
+    def _grid_aos(self):
+        """The Bloch AOs on the FFT grid, device (nk, ngrid, nao): what build() left resident,
+        evaluated on first use otherwise (an object restored by ``load``)."""
+        if self._ao_grid is None:
+            self._ao_grid = self._eval_ao(self.grids_coords())
+        return self._ao_grid
+
+    def get_rho(self, dm, hermi=1):
+        """Electron density on the FFT grid, rho[g] = (1/nk) sum_k sum_mn chi_k[g,m] D_k[m,n]
+        conj(chi_k[g,n]) (PySCF fft_jk.get_j_kpts' rhoR; integrates to the electron count with the
+        weight vol/ngrid): (nset, ngrid), or (ngrid,) for a single dm (nk, nao, nao).  hermi=1:
+        the dms are Hermitian, rho is returned real after checking max |Im| <= 1e-10 max |rho|;
+        hermi=0: complex."""
+        d = self.device
+        if d.sharded(self):
+            raise NotImplementedError("get_rho on a k-sharded object")
+        self._kmesh()
+        dms, ddms = _dms_to_dev(self, dm)
+        f = self._grid_aos()
+        nk, ngrid, nao = f.shape
+        nset = ddms.shape[0]
+        rho = d.empty((nset, ngrid))
+        d.ctx.call("fisdf_get_rho", _lib.ptr(f), ngrid * nao, nk, ngrid, nao, _lib.ptr(ddms), nset,
+                   _lib.ptr(rho))
+        out = d.to_host(rho)
+        if hermi == 1:
+            if abs(out.imag).max() > 1e-10 * abs(out).max():
+                raise ValueError("get_rho(hermi=1): the density is not real (max |Im rho| = "
+                                 f"{abs(out.imag).max():.3e}); pass hermi=0 for general dms")
+            out = np.ascontiguousarray(out.real)
+        nd = np.ndim(dm)
+        return out[0] if nd < 4 else out
 
     def madelung(self):
         """``tools.pbc.madelung(cell, kpts)`` [pyscf] for this k-mesh (host scalar, cached)."""
@@ -917,6 +967,7 @@ def _dms_to_dev(df_obj, dm_kpts):
 def get_j_kpts(df_obj, dm_kpts, hermi=1, kpts=np.zeros((1, 3)), kpts_band=None, exxdiv=None):
     """fftisdf.py:133-171 (kpts_band: J at any band k-points, next-4)."""
     assert exxdiv is None
+    _check_j_method(df_obj)
     dms, ddms = _dms_to_dev(df_obj, dm_kpts)
     band = _band_of(df_obj, np.asarray(kpts), kpts_band)
     return _finish_j(_get_j_dev(df_obj, ddms, band), dm_kpts, kpts, kpts_band)
@@ -964,9 +1015,82 @@ def _band_aos(df_obj, kb):
     return cache[key]
 
 
-def _get_j_dev(df_obj, ddms, band=None):
+def _check_j_method(df_obj):
+    if df_obj.j_method not in df_obj.J_METHODS:
+        raise ValueError(f"ISDF.j_method must be one of {list(df_obj.J_METHODS)}, "
+                         f"not {df_obj.j_method!r}")
+
+
+# device bytes of band AOs on the FFT grid evaluated at a time (J at off-mesh band k-points)
+BAND_BLOCK_BYTES = 1 << 28
+
+
+def _get_j_fft_dev(df_obj, ddms, band=None, omega=None):
+    """The exact FFT-grid J on the device (PySCF fft_jk.get_j_kpts), j_method = "fft", with the
+    Coulomb kernel coulG(omega) (None: the omega this object was fitted with): on the
+    k-mesh one fisdf_get_j_fft over the resident Bloch AOs; at band k-points that are all on the
+    mesh rows of that; otherwise rho and v once, then the Gram of the band AOs on the full FFT
+    grid weighted by v, a block of band points at a time.  A kpts_band that mixes on-mesh and
+    off-mesh points takes the second route for all of them: the on-mesh ones are evaluated again
+    on the grid rather than taken as rows of the k-mesh J (the same J to rounding)."""
+    d = df_obj.device
+    if d.sharded(df_obj):
+        raise NotImplementedError('j_method = "fft" on a k-sharded object')
+    cell = df_obj.cell
+    f = df_obj._grid_aos()
+    nk, ngrid, nao = f.shape
+    nset = ddms.shape[0]
+    if omega is None:
+        omega = getattr(df_obj, "_fit_omega", 0.0)
+    omega = float(omega)
+    a = np.asarray(cell.lattice_vectors(), float)
+    km_c, km_p = _lib.iarr(df_obj._kmesh())
+    mesh_c, mesh_p = _lib.iarr(df_obj.mesh)
+    a_c, a_p = _lib.darr(a.ravel())
+    on_mesh = None
+    if band is not None:
+        try:
+            on_mesh, _ = df_obj._kidx(band)
+        except ValueError:
+            on_mesh = None
+    if band is None or on_mesh is not None:
+        vj = d.empty(ddms.shape)
+        d.ctx.call("fisdf_get_j_fft", _lib.ptr(f), ngrid * nao, km_p, mesh_p, a_p, nao,
+                   _lib.ptr(ddms), nset, omega, None, 0, _lib.ptr(vj))
+        if on_mesh is not None:
+            vj = vj[:, d.torch.as_tensor(on_mesh.astype(np.int64), device=vj.device)]
+        return vj
+    rho = d.empty((nset, ngrid))
+    v = d.empty((nset, ngrid))
+    d.ctx.call("fisdf_get_rho", _lib.ptr(f), ngrid * nao, nk, ngrid, nao, _lib.ptr(ddms), nset,
+               _lib.ptr(rho))
+    d.ctx.call("fisdf_coulomb_potential", _lib.ptr(rho), nset, mesh_p, a_p, omega, _lib.ptr(v))
+    nb = len(band)
+    vj = d.empty((nset, nb, nao, nao))
+    blk = max(1, int(BAND_BLOCK_BYTES // (16 * ngrid * nao)))
+    coords = df_obj.grids_coords()
+    scale = abs(np.linalg.det(a)) / ngrid
+    for b0 in range(0, nb, blk):
+        b1 = min(nb, b0 + blk)
+        if df_obj.ao_on_gpu and hasattr(cell, "shells"):
+            from .ao import eval_ao_band_gpu
+            fb = eval_ao_band_gpu(d, cell, coords, band[b0:b1])
+        else:                                   # a PySCF-protocol cell: pbc_eval_gto at kb
+            fb = d.to_dev(bloch_ao(cell, coords, band[b0:b1]))
+        out = d.empty((nset, b1 - b0, nao, nao))
+        d.ctx.call("fisdf_weighted_gram", _lib.ptr(fb), ngrid * nao, b1 - b0, ngrid, nao,
+                   _lib.ptr(v), nset, 0, scale, _lib.ptr(out))
+        vj[:, b0:b1] = out
+        del fb
+    return vj
+
+
+def _get_j_dev(df_obj, ddms, band=None, omega=None):
     """vj on the device (fftisdf.py:150-166) for device dms (nset, nk, nao, nao); band: J at
-    those k-points instead (nset, nband, nao, nao)."""
+    those k-points instead (nset, nband, nao, nao).  omega: see _get_j_fft_dev (the ISDF J's
+    kernel is in the fitted W_0)."""
+    if df_obj.j_method == "fft":
+        return _get_j_fft_dev(df_obj, ddms, band, omega)
     st = df_obj._dev_state
     assert st is not None and "W0" in st, "call build() first"
     d = df_obj.device

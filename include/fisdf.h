@@ -486,6 +486,39 @@ int fisdf_get_j_band_rows(fisdf_ctx* ctx, const void* d_X, const void* d_W0, con
                           int nset, int nk, int nip, int nao, const void* d_Xb, int nkb, int i0,
                           int i1, void* d_vj);
 
+/* ---- exact FFT-grid J and electron density (PySCF fft_jk.get_j_kpts) ----------------------
+ * J without the ISDF fit: the density of the Bloch AOs d_f (nk, ngrid, nao) c128 (k blocks
+ * f_kstride >= ngrid * nao elements apart) on the FFT grid, its Coulomb potential by one forward
+ * and one inverse 3-D FFT, and the AO Gram weighted by that potential.  Each of the two AO
+ * kernels reads d_f once per 4 sets, forms no grid x nao temporary and sums in a fixed order
+ * (repeated calls agree bit for bit).  Arguments are checked on the host and a refused call
+ * leaves its output untouched; a mesh the FFT does not take is found when the transform is
+ * reached, by which time earlier stages may have written the context's scratch arena, nothing
+ * else.  Asynchronous.
+ *
+ * The density: d_rho[s][g] = (1/nk) sum_k sum_mn f_k[g,m] D[s][k][m,n] conj(f_k[g,n]); d_dms
+ * (nset, nk, nao, nao), d_rho (nset, ngrid), complex (real up to rounding for Hermitian D). */
+int fisdf_get_rho(fisdf_ctx* ctx, const void* d_f, long f_kstride, int nk, int ngrid, int nao,
+                  const void* d_dms, int nset, void* d_rho);
+/* d_v[s] = ifft(coulG(G, omega) fft(d_rho[s])) on `mesh` (both (nset, ngrid) c128; coulG at k = 0
+ * with G = 0 dropped, omega as in fisdf_set_omega but given here, the context's setting is not
+ * read).  The inverse transform is the forward one between two conjugations.  A mesh the FFT
+ * does not take fails with d_v untouched. */
+int fisdf_coulomb_potential(fisdf_ctx* ctx, const void* d_rho, int nset, const int mesh[3],
+                            const double a[9], double omega, void* d_v);
+/* d_out[s][k][m][n] = scale sum_g conj(f_k[g,m]) v_s[g] f_k[g,n], with conj(v_s[g]) when conj_v
+ * is not 0; d_v (nset, ngrid), d_out (nset, nk, nao, nao).  The grid is split among workgroups
+ * and the partial blocks are summed in split order. */
+int fisdf_weighted_gram(fisdf_ctx* ctx, const void* d_f, long f_kstride, int nk, int ngrid,
+                        int nao, const void* d_v, int nset, int conj_v, double scale, void* d_out);
+/* The three stages back to back with scale = vol / ngrid: d_vj (nset, nk, nao, nao) for the
+ * k-mesh, or, with d_fband (nband, ngrid, nao) the AOs at band k-points on the same grid,
+ * d_vj (nset, nband, nao, nao) at those (d_fband NULL: the k-mesh).  rho and v live in the
+ * context's scratch arena. */
+int fisdf_get_j_fft(fisdf_ctx* ctx, const void* d_f, long f_kstride, const int kmesh[3],
+                    const int mesh[3], const double a[9], int nao, const void* d_dms, int nset,
+                    double omega, const void* d_fband, int nband, void* d_vj);
+
 /* ---- ISDF 4-index integrals (get_eri / ao2mo surface) --------------------------
  * eri[i*n2+j][k*n4+l] = sum_IJ W_q[I,J] conj(A1[I,i]) A2[I,j] conj(A3[J,k]) A4[J,l] with
  * A_s = X_{kidx[s]} C_s, q = k2 - k1 (fftdf-with-k-lstsq.py:221-232).  d_Wq: the (nip,nip)
