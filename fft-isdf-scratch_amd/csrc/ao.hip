@@ -256,25 +256,42 @@ int eval_ao(hipStream_t s, const double* d_coords, int ng, int natm, const doubl
   // the host tables must outlive the asynchronous copies
   FISDF_HIP(hipStreamSynchronize(s));
   const long ncol = nth;
-  if (band) {
-    const long tot = ncol * nkb;
-    hipLaunchKernelGGL(bloch_band_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, F,
-                       ncol, nT, (const cplx*)(b + oP), nkb, chi);
-    FISDF_HIP(hipGetLastError());
-    return 0;
-  }
+  if (band) return bloch_band(s, F, ncol, nT, (const cplx*)(b + oP), nkb, chi);
+  return bloch_dft(s, F, ncol, kmesh, chi);
+}
+
+int bloch_band(hipStream_t s, const double* F, long ncol, int nT, const cplx* ph, int nkb,
+               cplx* chi) {
+  FISDF_CHECK(ncol >= 0 && nT >= 0 && nkb >= 1, "bloch_band: bad sizes");
+  const long tot = ncol * nkb;
+  FISDF_CHECK((tot + 255) / 256 < (1L << 31), "bloch_band: too many columns");
+  if (tot == 0) return 0;
+  hipLaunchKernelGGL(bloch_band_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, F,
+                     ncol, nT, ph, nkb, chi);
+  FISDF_HIP(hipGetLastError());
+  return 0;
+}
+
+int bloch_dft(hipStream_t s, const double* F, long ncol, const int kmesh[3], cplx* chi,
+              int* route) {
+  FISDF_CHECK(kmesh[0] >= 1 && kmesh[1] >= 1 && kmesh[2] >= 1 && ncol >= 0,
+              "bloch_dft: bad sizes");
+  // the generic kernel takes any k-mesh: only the register route is read from the plan
+  const bool reg = kmesh_route(kmesh, ncol).route == KM_REG;
+  const long tot = ncol * kmesh[0] * kmesh[1] * kmesh[2];
+  FISDF_CHECK(reg || (tot + 255) / 256 < (1L << 31), "bloch_dft: too many columns");
+  if (route) *route = reg ? KM_REG : KM_LDS;
+  if (ncol == 0) return 0;
 #define FISDF_BD(x, y, z)                                                                      \
-  if (kmesh[0] == x && kmesh[1] == y && kmesh[2] == z) {                                       \
+  if (reg && kmesh[0] == x && kmesh[1] == y && kmesh[2] == z) {                                \
     hipLaunchKernelGGL((bloch_dft_reg_kernel<x, y, z>),                                         \
                        dim3((unsigned)std::min<long>((ncol + 63) / 64, 65536)), dim3(64), 0, s, F, \
                        ncol, chi);                                                             \
     FISDF_HIP(hipGetLastError());                                                              \
     return 0;                                                                                  \
   }
-  FISDF_BD(1, 1, 1) FISDF_BD(1, 1, 2) FISDF_BD(2, 2, 2) FISDF_BD(3, 3, 1) FISDF_BD(3, 3, 3)
-  FISDF_BD(4, 4, 4) FISDF_BD(2, 2, 1) FISDF_BD(1, 2, 2) FISDF_BD(4, 4, 1) FISDF_BD(2, 2, 4)
+  FISDF_KM_REG_MESHES(FISDF_BD)
 #undef FISDF_BD
-  const long tot = ncol * nimg;
   hipLaunchKernelGGL(bloch_dft_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, F,
                      ncol, kmesh[0], kmesh[1], kmesh[2], chi);
   FISDF_HIP(hipGetLastError());

@@ -1741,6 +1741,10 @@ int fisdf_build_x4(fisdf_ctx* c, const void* Xv, int nip, int nao, const int kme
 // buffer instead of the arena (whose users are ordered on c->stream only)
 static int build_x4_on(fisdf_ctx* c, hipStream_t st, fisdf_ctx::DevBuf* wsb, const void* Xv,
                        int nip, int nao, const int kmesh[3], const double a[9], void* x4v) {
+  // before anything is enqueued: a k-mesh no k-mesh transform takes (the y build would refuse it
+  // only after its first GEMM)
+  FISDF_TRY(kmesh_check(kmesh, "build_x4"));
+  FISDF_CHECK(nip >= 1 && nao >= 1, "build_x4: bad sizes");
   StageTimer tm(c, FISDF_ST_X4, st);
   const int nk = kmesh[0] * kmesh[1] * kmesh[2];
   const cplx* phase;
@@ -1812,6 +1816,8 @@ int fisdf_build_y_qs(fisdf_ctx* c, const void* fv, long f_kstride, int g0, int n
                      const int* h_qs, int nq, void* yTv) {
   FISDF_TRY(device_guard(c));
   FISDF_CHECK(g0 >= 0 && nblk >= 0 && g0 + nblk <= ngrid, "build_y: block out of range");
+  // kmesh_y's own k-mesh checks come only after the fx GEMM has been enqueued
+  FISDF_TRY(kmesh_check(kmesh, "build_y"));
   StageTimer tm(c, FISDF_ST_Y);
   const int nk = kmesh[0] * kmesh[1] * kmesh[2];
   FISDF_TRY(check_qlist(h_qs, nq, nk, "build_y"));
@@ -1919,6 +1925,8 @@ int fisdf_build_y_qs(fisdf_ctx* c, const void* fv, long f_kstride, int g0, int n
 int fisdf_build_y(fisdf_ctx* c, const void* fv, long f_kstride, int g0, int nblk, int ngrid,
                   const void* Xv, int nip, int nao, const int kmesh[3], const double a[9],
                   int q0, int q1, void* yTv) {
+  t_cur_ctx = c;
+  FISDF_CHECK(kmesh && kmesh[0] >= 1 && kmesh[1] >= 1 && kmesh[2] >= 1, "build_y: bad k-mesh");
   const int nk = kmesh[0] * kmesh[1] * kmesh[2];
   FISDF_CHECK(0 <= q0 && q0 < q1 && q1 <= nk, "build_y: bad q range");
   std::vector<int> qs = q_range(q0, q1);
@@ -3347,6 +3355,27 @@ int fisdf_get_k_rows_local(fisdf_ctx* c, const void* Xv, const void* Ws_rows, co
                      kmesh, a, i0, i1, vkv);
 }
 
+// get_k's transform pair in place on B1 (nk rows of bn columns; B2 a buffer of the same size):
+// rho_s = Phi rho_k (:215), V_s = W_s * Re(rho_s) (:219), V_k = Phi^T V_s (:222).  use_reg: one
+// register pass per column where the k-mesh has one (round 6, C3: 0.50 -> ~0.2 ms; *reg_ran);
+// otherwise two dense Phi GEMMs
+static int k_wsrho_pair(fisdf_ctx* c, const int kmesh[3], const cplx* phase, cplx* B1, cplx* B2,
+                        long bn, const double* Ws_rows, long ws_Rstride, bool use_reg,
+                        unsigned long long* mon, bool* reg_ran) {
+  const int nk = kmesh[0] * kmesh[1] * kmesh[2];
+  *reg_ran = false;
+  if (use_reg) FISDF_TRY(k_wsrho_reg(c->stream, B1, bn, kmesh, Ws_rows, ws_Rstride, mon, reg_ran));
+  if (*reg_ran) return 0;
+  // rho_s = Phi rho_k (:215), real (:216), and V_s = W_s * rho_s^T (:219) for the block
+  // rows, both in the GEMM's epilogue (EPI_WSRHO: Re(W_s) Re(.), max |Im rho_s| recorded)
+  FISDF_TRY(zgemm(c->stream, OP_N, OP_N, nk, bn, nk, ONE, phase, nk, 0, B1, bn, 0, ZERO, B2, bn, 0,
+                  1, 1, (cplx*)(void*)Ws_rows, EPI_WSRHO, mon, GEMM_FULL, ws_Rstride));
+  // V_k = Phi^T V_s (:222)
+  FISDF_TRY(zgemm(c->stream, OP_T, OP_N, nk, bn, nk, ONE, phase, nk, 0, B2, bn, 0, ZERO, B1, bn, 0,
+                  1));
+  return 0;
+}
+
 static int get_k_block(fisdf_ctx* c, const void* Xv, const double* Ws_rows, long ws_Rstride,
                        const void* dmsv, int nset, int nip, int nao, const int kmesh[3],
                        const double a[9], int i0, int i1, void* vkv) {
@@ -3388,23 +3417,11 @@ static int get_k_block(fisdf_ctx* c, const void* Xv, const double* Ws_rows, long
     } else {
       FISDF_TRY(zgemm(c->stream, OP_N, OP_T, nb, nip, nao, ONE, T, nao, ba, X, nao, xs, ZERO, B1,
                       nip, bn, nk));
-      // round 6: the transform pair and the product in one register pass per column (C3: 0.50
-      // -> ~0.2 ms); FISDF_K_DFT=0 (read per call: the GPU tests compare) keeps the GEMMs
-      bool done = false;
+      // FISDF_K_DFT=0 (read per call: the GPU tests compare) keeps the GEMMs
       const char* kd = getenv("FISDF_K_DFT");
-      if (!(kd && kd[0] == '0'))
-        FISDF_TRY(k_wsrho_reg(c->stream, B1, bn, kmesh, Ws_rows, ws_Rstride, c->maximag + 2,
-                              &done));
-      if (!done) {
-        // rho_s = Phi rho_k (:215), real (:216), and V_s = W_s * rho_s^T (:219) for the block
-        // rows, both in the GEMM's epilogue (EPI_WSRHO: Re(W_s) Re(.), max |Im rho_s| recorded)
-        FISDF_TRY(zgemm(c->stream, OP_N, OP_N, nk, bn, nk, ONE, phase, nk, 0, B1, bn, 0, ZERO, B2,
-                        bn, 0, 1, 1, (cplx*)(void*)Ws_rows, EPI_WSRHO, c->maximag + 2, GEMM_FULL,
-                        ws_Rstride));
-        // V_k = Phi^T V_s (:222)
-        FISDF_TRY(zgemm(c->stream, OP_T, OP_N, nk, bn, nk, ONE, phase, nk, 0, B2, bn, 0, ZERO, B1,
-                        bn, 0, 1));
-      }
+      bool reg = false;
+      FISDF_TRY(k_wsrho_pair(c, kmesh, phase, B1, B2, bn, Ws_rows, ws_Rstride,
+                             !(kd && kd[0] == '0'), c->maximag + 2, &reg));
     }
     // K_k (block part) = X_k[I]^H (V_k[I, :] X_k)  (:225)
     FISDF_TRY(zgemm(c->stream, OP_N, OP_N, nb, nao, nip, ONE, B1, nip, bn, X, nao, xs, ZERO, T,
@@ -3418,6 +3435,227 @@ static int get_k_block(fisdf_ctx* c, const void* Xv, const double* Ws_rows, long
 int fisdf_get_k(fisdf_ctx* c, const void* Xv, const void* Wsv, const void* dmsv, int nset, int nip,
                 int nao, const int kmesh[3], const double a[9], void* vkv) {
   return fisdf_get_k_rows(c, Xv, Wsv, dmsv, nset, nip, nao, kmesh, a, 0, nip, vkv);
+}
+
+// ---- the separable k-mesh transforms piece by piece, for tests of their dispatch --------------
+int fisdf_kmesh_plan(const int kmesh[3], long ncol, int nao, int nip, int m, long* h_route,
+                     int* h_half_count, int* h_runs, int runs_cap, int* h_nruns, int* h_fused,
+                     int* h_slots, long* h_fused_bytes) {
+  t_cur_ctx = nullptr;
+  FISDF_CHECK(kmesh && kmesh[0] >= 1 && kmesh[1] >= 1 && kmesh[2] >= 1 && ncol >= 0,
+              "kmesh_plan: bad sizes");
+  const KmeshPlan kp = kmesh_route(kmesh, ncol);
+  if (h_route) {
+    h_route[0] = kp.route;
+    h_route[1] = kp.CT;
+    h_route[2] = (long)kp.lds;
+  }
+  if (h_half_count) *h_half_count = kmesh_half_count(kmesh);
+  if (h_runs || h_nruns) {
+    std::vector<int> runs;
+    FISDF_TRY(kmesh_rep_runs(kmesh, &runs));
+    const int nr = (int)runs.size() / 2;
+    FISDF_CHECK(!h_runs || runs_cap >= nr, "kmesh_plan: h_runs too short");
+    if (h_nruns) *h_nruns = nr;
+    if (h_runs) std::memcpy(h_runs, runs.data(), sizeof(int) * runs.size());
+  }
+  YFusedPlan yp;
+  y_fused_plan(kmesh, nao, &yp);
+  if (h_fused) {
+    h_fused[0] = yp.applies ? 1 : 0;
+    h_fused[1] = yp.nA;
+    h_fused[2] = yp.nB;
+    h_fused[3] = yp.nkc;
+  }
+  if (h_slots)
+    for (int i = 0; i < 48; ++i) h_slots[i] = i < yp.nA ? yp.kA[i] : (i - yp.nA < yp.nB ? yp.kB[i - yp.nA] : -1);
+  if (h_fused_bytes) {
+    h_fused_bytes[0] = (long)yp.lds;
+    h_fused_bytes[1] = (long)y_fused_workspace(kmesh, nip, nao, m);
+  }
+  return 0;
+}
+
+// a device monitor word and a device q-list in the arena behind `extra` bytes of workspace
+static int kmesh_test_scratch(fisdf_ctx* c, size_t extra, const int* h_qs, int nq, char** work,
+                              unsigned long long** mon, int** dq) {
+  Carver cv;
+  const size_t oW = cv.take(extra), oM = cv.take(sizeof(unsigned long long)),
+               oQ = cv.take(sizeof(int) * (size_t)std::max(nq, 1));
+  void* base;
+  FISDF_TRY(arena_get(c, cv.off, &base));
+  *work = (char*)base + oW;
+  *mon = (unsigned long long*)((char*)base + oM);
+  *dq = (int*)((char*)base + oQ);
+  FISDF_HIP(hipMemsetAsync(*mon, 0, sizeof(unsigned long long), c->stream));
+  FISDF_TRY(upload_ints(c, h_qs, nq, *dq));
+  return 0;
+}
+
+static int kmesh_test_monitor(fisdf_ctx* c, const unsigned long long* mon, double* h_mon) {
+  unsigned long long bits = 0;
+  FISDF_HIP(hipMemcpyAsync(&bits, mon, sizeof(bits), hipMemcpyDeviceToHost, c->stream));
+  FISDF_HIP(hipStreamSynchronize(c->stream));
+  if (h_mon) std::memcpy(h_mon, &bits, sizeof(double));
+  return 0;
+}
+
+int fisdf_kmesh_y_ex(fisdf_ctx* c, const void* FX, long ncol, const int kmesh[3], const int* h_qs,
+                     int nq, int m, void* yT, long qs, long Is, long goff, int half, int conj_out,
+                     double* h_mon, int* h_route) {
+  FISDF_TRY(device_guard(c));
+  if (h_route) *h_route = -1;
+  FISDF_CHECK(FX && yT && kmesh && ncol >= 0 && m >= 1 && qs >= 0 && Is >= 0 && goff >= 0,
+              "kmesh_y_ex: bad arguments");
+  FISDF_TRY(kmesh_check(kmesh, "kmesh_y_ex"));
+  FISDF_TRY(check_qlist(h_qs, nq, kmesh[0] * kmesh[1] * kmesh[2], "kmesh_y_ex"));
+  const KmeshPlan kp = kmesh_route(kmesh, ncol);
+  FISDF_CHECK(kp.route != KM_REFUSED, "kmesh_y_ex: too many columns");
+  FISDF_CHECK(!conj_out || kp.route == KM_REG,
+              "kmesh_y_ex: conj_out needs the register kernel's k-mesh");
+  char* work;
+  unsigned long long* mon;
+  int* dq;
+  FISDF_TRY(kmesh_test_scratch(c, 0, h_qs, nq, &work, &mon, &dq));
+  FISDF_TRY(kmesh_y(c->stream, (const cplx*)FX, ncol, kmesh, h_qs, dq, nq, m, (cplx*)yT, qs, Is,
+                    goff, half != 0, mon, conj_out != 0));
+  FISDF_TRY(kmesh_test_monitor(c, mon, h_mon));
+  if (h_route && ncol > 0) *h_route = kp.route;
+  return 0;
+}
+
+int fisdf_y_fused_ex(fisdf_ctx* c, const void* X, int nip, int nao, const void* F, long fks, int m,
+                     const int kmesh[3], const int* h_qs, int nq, void* yT, long qs, long Is,
+                     long goff, unsigned long long rmask, int* h_handled) {
+  FISDF_TRY(device_guard(c));
+  if (h_handled) *h_handled = 0;
+  FISDF_CHECK(X && F && yT && kmesh && nip >= 1 && nao >= 1 && m >= 1 && fks >= 0 && qs >= 0 &&
+                  Is >= 0 && goff >= 0,
+              "y_fused_ex: bad arguments");
+  FISDF_TRY(kmesh_check(kmesh, "y_fused_ex"));
+  FISDF_TRY(check_qlist(h_qs, nq, kmesh[0] * kmesh[1] * kmesh[2], "y_fused_ex"));
+  if (!y_fused_applies(kmesh, nao)) return 0;
+  const size_t yw = y_fused_workspace(kmesh, nip, nao, m);
+  FISDF_CHECK(yw > 0, "y_fused_ex: no workspace for a k-mesh the fused kernel takes");
+  char* work;
+  unsigned long long* mon;
+  int* dq;
+  FISDF_TRY(kmesh_test_scratch(c, yw, h_qs, nq, &work, &mon, &dq));
+  bool done = false;
+  FISDF_TRY(y_fused(c->stream, (const cplx*)X, nip, nao, (const cplx*)F, fks, m, kmesh, h_qs, nq,
+                    (cplx*)yT, qs, Is, goff, mon, (cplx*)work, yw, rmask, &done));
+  FISDF_HIP(hipStreamSynchronize(c->stream));
+  if (h_handled) *h_handled = done ? 1 : 0;
+  return 0;
+}
+
+int fisdf_y_fused_stream_ex(fisdf_ctx* c, const void* x0, int ng0, int nao, const int* h_piv,
+                            int nip, int rows, const void* F, long fks, int m, const int kmesh[3],
+                            const int* h_qs, int nq, void* yT, long qs, long Is, long goff,
+                            unsigned long long rmask, int two_streams, int* h_handled,
+                            int* h_err) {
+  FISDF_TRY(device_guard(c));
+  if (h_handled) *h_handled = 0;
+  if (h_err) *h_err = 0;
+  FISDF_CHECK(x0 && F && yT && kmesh && h_piv && ng0 >= 1 && nip >= 1 && nao >= 1 && m >= 1 &&
+                  fks >= 0 && qs >= 0 && Is >= 0 && goff >= 0,
+              "y_fused_stream_ex: bad arguments");
+  FISDF_CHECK(rows >= 16 && rows % 16 == 0 && rows <= 64 * 16, "y_fused_stream_ex: bad row block");
+  for (int i = 0; i < nip; ++i)
+    FISDF_CHECK(h_piv[i] >= 0 && h_piv[i] < ng0, "y_fused_stream_ex: pivot out of range");
+  FISDF_TRY(kmesh_check(kmesh, "y_fused_stream_ex"));
+  FISDF_TRY(check_qlist(h_qs, nq, kmesh[0] * kmesh[1] * kmesh[2], "y_fused_stream_ex"));
+  if (!y_fused_applies(kmesh, nao)) return 0;
+  const size_t yw = y_fused_workspace(kmesh, nip, nao, m);
+  FISDF_CHECK(yw > 0, "y_fused_stream_ex: no workspace for a k-mesh the fused kernel takes");
+  // behind the workspace: the pivots, then the progress word (already "done": the bounded wait of
+  // the XT kernel never spins) and the error flag
+  Carver cv;
+  const size_t oW = cv.take(yw), oP = cv.take(sizeof(int) * ((size_t)nip + 2));
+  void* base;
+  FISDF_TRY(arena_get(c, cv.off, &base));
+  int* dpiv = (int*)((char*)base + oP);
+  std::vector<int> h(h_piv, h_piv + nip);
+  h.push_back(kSelDone);
+  h.push_back(0);
+  FISDF_TRY(upload_ints(c, h.data(), nip + 2, dpiv));
+  hipStream_t s2 = nullptr;
+  hipEvent_t ea = nullptr, eb = nullptr;
+  int rc = 0;
+  bool done = false;
+  if (two_streams) {
+    if (hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&ea, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&eb, hipEventDisableTiming) != hipSuccess) {
+      (void)hipGetLastError();
+      set_error("fisdf: y_fused_stream_ex: could not create the second stream");
+      rc = -2;
+    }
+  }
+  if (rc == 0)
+    rc = y_fused_stream(c->stream, (const cplx*)x0, ng0, nao, dpiv, dpiv + nip, dpiv + nip + 1, nip,
+                        rows, (const cplx*)F, fks, m, kmesh, h_qs, nq, (cplx*)yT, qs, Is, goff,
+                        (cplx*)((char*)base + oW), yw, rmask, &done, s2, ea, eb);
+  int err = 0;
+  if (s2) (void)hipStreamSynchronize(s2);
+  if (rc == 0 && hipMemcpyAsync(&err, dpiv + nip + 1, sizeof(int), hipMemcpyDeviceToHost,
+                                c->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("fisdf: y_fused_stream_ex: reading the error flag failed");
+    rc = -2;
+  }
+  (void)hipStreamSynchronize(c->stream);
+  if (ea) (void)hipEventDestroy(ea);
+  if (eb) (void)hipEventDestroy(eb);
+  if (s2) (void)hipStreamDestroy(s2);
+  if (rc != 0) return rc;
+  if (h_handled) *h_handled = done ? 1 : 0;
+  if (h_err) *h_err = err;
+  return 0;
+}
+
+int fisdf_k_wsrho_ex(fisdf_ctx* c, void* B, long ncol, const int kmesh[3], const double a[9],
+                     const void* Ws, long ws_Rstride, int use_reg, double* h_mon,
+                     int* h_handled) {
+  FISDF_TRY(device_guard(c));
+  if (h_handled) *h_handled = 0;
+  FISDF_CHECK(B && Ws && kmesh && a && ncol >= 1 && ncol < (1L << 31) && ws_Rstride >= ncol,
+              "k_wsrho_ex: bad arguments");
+  FISDF_TRY(kmesh_check(kmesh, "k_wsrho_ex"));
+  const int nk = kmesh[0] * kmesh[1] * kmesh[2];
+  const cplx* phase;
+  FISDF_TRY(get_phase(c, kmesh, a, &phase));
+  char* work;
+  unsigned long long* mon;
+  int* dq;
+  FISDF_TRY(kmesh_test_scratch(c, sizeof(cplx) * (size_t)nk * ncol, nullptr, 0, &work, &mon, &dq));
+  bool reg = false;
+  FISDF_TRY(k_wsrho_pair(c, kmesh, phase, (cplx*)B, (cplx*)work, ncol, (const double*)Ws,
+                         ws_Rstride, use_reg != 0, mon, &reg));
+  FISDF_TRY(kmesh_test_monitor(c, mon, h_mon));
+  if (h_handled) *h_handled = reg ? 1 : 0;
+  return 0;
+}
+
+int fisdf_bloch_dft_ex(fisdf_ctx* c, const void* F, long ncol, const int kmesh[3], void* chi,
+                       int* h_route) {
+  FISDF_TRY(device_guard(c));
+  if (h_route) *h_route = -1;
+  FISDF_CHECK(F && chi && kmesh && ncol >= 0, "bloch_dft_ex: bad arguments");
+  int route = -1;
+  FISDF_TRY(bloch_dft(c->stream, (const double*)F, ncol, kmesh, (cplx*)chi, &route));
+  FISDF_HIP(hipStreamSynchronize(c->stream));
+  if (h_route && ncol > 0) *h_route = route;
+  return 0;
+}
+
+int fisdf_bloch_band_ex(fisdf_ctx* c, const void* F, long ncol, int nT, const void* ph, int nkb,
+                        void* chi) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(F && ph && chi, "bloch_band_ex: bad arguments");
+  FISDF_TRY(bloch_band(c->stream, (const double*)F, ncol, nT, (const cplx*)ph, nkb, (cplx*)chi));
+  FISDF_HIP(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 // ---- composite entries --------------------------------------------------------

@@ -135,8 +135,46 @@ int eval_ao(hipStream_t s, const double* d_coords, int ng, int natm, const doubl
 int kmesh_y(hipStream_t s, const cplx* FX, long ncol, const int kmesh[3], const int* h_qs,
             const int* d_qs, int nq, int m, cplx* yT, long qs, long Is, long goff, bool half,
             unsigned long long* mon, bool conj_out = false);
+// the k-meshes with compile-time instantiations of the register kernels (kmesh_y_reg_kernel,
+// y_fused_kernel, k_wsrho_reg_kernel, bloch_dft_reg_kernel): the one list every dispatch expands
+#define FISDF_KM_REG_MESHES(X)                                                                 \
+  X(1, 1, 1) X(1, 1, 2) X(2, 2, 2) X(3, 3, 1) X(3, 3, 3) X(4, 4, 4) X(2, 2, 1) X(1, 2, 2)       \
+  X(4, 4, 1) X(2, 2, 4)
+// Which kernel a separable k-mesh transform over ncol columns runs; kmesh_y(),
+// kmesh_y_reg_applies(), k_wsrho_reg() and bloch_dft() branch on it.  KM_REG: a listed k-mesh
+// (at most 64 points) and ncol < 2^31.  KM_LDS: kmesh_y_kernel on tiles of CT columns (64, halved
+// down to 8 until the nk x (CT + 1) tile and the twiddles fit 64 KB) with `lds` bytes of dynamic
+// LDS (the tile, the twiddles and the nk-entry source table).  KM_REFUSED: an axis outside 1..16,
+// more than 160 KB of LDS, or 2^31 tiles; CT and lds are still those of the LDS rule when the
+// axes are in range.
+enum KmeshRoute { KM_REG = 0, KM_LDS = 1, KM_REFUSED = 2 };
+struct KmeshPlan {
+  int route;
+  int CT;
+  size_t lds;
+};
+KmeshPlan kmesh_route(const int kmesh[3], long ncol);
+// 0 when some kmesh_route of this k-mesh runs, else the error a transform over it would raise
+int kmesh_check(const int kmesh[3], const char* who);
 // whether kmesh_y runs its register kernel for this k-mesh and column count (no device q-list)
 bool kmesh_y_reg_applies(const int kmesh[3], long ncol);
+// the fused kernel's plan for a k-mesh and nao: whether it applies, the k of its chunk A / chunk B
+// slots in slot order, its dynamic LDS bytes and the K chunks (of 28) per slot
+struct YFusedPlan {
+  bool applies;
+  int nA, nB;
+  int kA[16], kB[32];
+  size_t lds;
+  int nkc;
+};
+void y_fused_plan(const int kmesh[3], int nao, YFusedPlan* out);
+// chi[k][col] = sum_R exp(+2 pi i sum_a r_a k_a / n_a) F[R][col] over the k-mesh (the tail of
+// eval_ao): the register kernel on a KM_REG route, else one thread per (k, column); *route (may
+// be null) tells which.  bloch_band: chi[k][col] = sum_t ph[t][k] F[t][col] for nkb band k-points
+int bloch_dft(hipStream_t s, const double* F, long ncol, const int kmesh[3], cplx* chi,
+              int* route = nullptr);
+int bloch_band(hipStream_t s, const double* F, long ncol, int nT, const cplx* ph, int nkb,
+               cplx* chi);
 // get_k's rho_s = Phi rho_k, V_s = W_s * Re(rho_s), V_k = Phi^T V_s in place on B (nk rows of
 // ncol columns; W_s row s at Ws + s * ws_Rstride) for the register k-meshes; *handled = false
 // (nothing enqueued) otherwise.  max |Im rho_s| into *mon

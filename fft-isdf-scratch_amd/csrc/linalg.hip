@@ -1549,14 +1549,46 @@ int kmesh_rep_runs(const int kmesh[3], std::vector<int>* runs) {
   return 0;
 }
 
-#define FISDF_KM_REG_MESHES(X)                                                                 \
-  X(1, 1, 1) X(1, 1, 2) X(2, 2, 2) X(3, 3, 1) X(3, 3, 3) X(4, 4, 4) X(2, 2, 1) X(1, 2, 2)       \
-  X(4, 4, 1) X(2, 2, 4)
+KmeshPlan kmesh_route(const int kmesh[3], long ncol) {
+  KmeshPlan p{KM_REFUSED, 0, 0};
+  for (int a = 0; a < 3; ++a)
+    if (kmesh[a] < 1 || kmesh[a] > KM_MAXN) return p;
+  const int nk = kmesh[0] * kmesh[1] * kmesh[2];
+  if (ncol < (1L << 31) && nk <= 64) {
+    bool on = false;
+#define FISDF_KM_HAS(a, b, c) on = on || (kmesh[0] == a && kmesh[1] == b && kmesh[2] == c);
+    FISDF_KM_REG_MESHES(FISDF_KM_HAS)
+#undef FISDF_KM_HAS
+    if (on) {
+      p.route = KM_REG;
+      return p;
+    }
+  }
+  int CT = 64;
+  while (CT > 8 && sizeof(cplx) * ((size_t)nk * (CT + 1) + 3 * KM_MAXN) > 64 * 1024) CT /= 2;
+  p.CT = CT;
+  p.lds = sizeof(cplx) * ((size_t)nk * (CT + 1) + 3 * KM_MAXN) + sizeof(int) * nk;
+  if (p.lds > 160 * 1024) return p;
+  if ((std::max<long>(ncol, 0) + CT - 1) / CT >= (1L << 31)) return p;
+  p.route = KM_LDS;
+  return p;
+}
+
+int kmesh_check(const int kmesh[3], const char* who) {
+  const std::string w(who);
+  FISDF_CHECK(kmesh[0] >= 1 && kmesh[1] >= 1 && kmesh[2] >= 1 && kmesh[0] <= KM_MAXN &&
+                  kmesh[1] <= KM_MAXN && kmesh[2] <= KM_MAXN,
+              w + ": k-mesh axes must be in 1..16");
+  FISDF_CHECK(kmesh_route(kmesh, 1).route != KM_REFUSED,
+              w + ": k-mesh too large for the LDS tile");
+  return 0;
+}
 
 int k_wsrho_reg(hipStream_t s, cplx* B, long ncol, const int kmesh[3], const double* Ws,
                 long ws_Rstride, unsigned long long* mon, bool* handled) {
   *handled = false;
   if (ncol <= 0) return 0;
+  if (kmesh_route(kmesh, ncol).route != KM_REG) return 0;
   const unsigned grid = (unsigned)std::max<long>(1, std::min<long>((ncol + 63) / 64, 32768));
 #define FISDF_KW(a, b, c)                                                                      \
   if (kmesh[0] == a && kmesh[1] == b && kmesh[2] == c) {                                       \
@@ -1572,11 +1604,7 @@ int k_wsrho_reg(hipStream_t s, cplx* B, long ncol, const int kmesh[3], const dou
 }
 
 bool kmesh_y_reg_applies(const int kmesh[3], long ncol) {
-  bool on = false;
-#define FISDF_KM_HAS(a, b, c) on = on || (kmesh[0] == a && kmesh[1] == b && kmesh[2] == c);
-  FISDF_KM_REG_MESHES(FISDF_KM_HAS)
-#undef FISDF_KM_HAS
-  return on && ncol < (1L << 31);
+  return kmesh_route(kmesh, ncol).route == KM_REG;
 }
 
 int kmesh_y(hipStream_t s, const cplx* FX, long ncol, const int kmesh[3], const int* h_qs,
@@ -1586,9 +1614,13 @@ int kmesh_y(hipStream_t s, const cplx* FX, long ncol, const int kmesh[3], const 
   for (int i = 0; i < nq; ++i)
     FISDF_CHECK(h_qs[i] >= 0 && h_qs[i] < nk && (i == 0 || h_qs[i] > h_qs[i - 1]),
                 "kmesh_y: q-list must be ascending and inside the k-mesh");
-  FISDF_CHECK(kmesh[0] <= KM_MAXN && kmesh[1] <= KM_MAXN && kmesh[2] <= KM_MAXN,
+  FISDF_CHECK(kmesh[0] >= 1 && kmesh[1] >= 1 && kmesh[2] >= 1 && kmesh[0] <= KM_MAXN &&
+                  kmesh[1] <= KM_MAXN && kmesh[2] <= KM_MAXN,
               "kmesh_y: k-mesh axes must be <= 16");
-  if (ncol < (1L << 31) && nk <= 64) {
+  FISDF_CHECK(ncol >= 0 && (m >= 1 || ncol == 0) && nq >= 0, "kmesh_y: bad sizes");
+  const KmeshPlan kp = kmesh_route(kmesh, ncol);
+  if (kp.route == KM_REG) {
+    if (ncol == 0) return 0;
     const int nc = (int)ncol;
     unsigned long long qmask = 0;
     for (int i = 0; i < nq; ++i) qmask |= 1ull << h_qs[i];
@@ -1609,15 +1641,17 @@ int kmesh_y(hipStream_t s, const cplx* FX, long ncol, const int kmesh[3], const 
 #undef FISDF_KM
   }
   FISDF_CHECK(!conj_out, "kmesh_y: conj_out needs the register kernel's k-mesh");
-  int CT = 64;
-  while (CT > 8 && sizeof(cplx) * ((size_t)nk * (CT + 1) + 3 * KM_MAXN) > 64 * 1024) CT /= 2;
-  const size_t lds = sizeof(cplx) * ((size_t)nk * (CT + 1) + 3 * KM_MAXN) + sizeof(int) * nk;
+  const int CT = kp.CT;
+  const size_t lds = kp.lds;
   FISDF_CHECK(lds <= 160 * 1024, "kmesh_y: k-mesh too large for the LDS tile");
   FISDF_CHECK(d_qs != nullptr, "kmesh_y: device q-list required for this k-mesh");
+  FISDF_CHECK(kp.route == KM_LDS, "kmesh_y: too many columns");
   const long tiles = (ncol + CT - 1) / CT;
-  FISDF_CHECK(tiles < (1L << 31), "kmesh_y: too many columns");
   if (tiles == 0) return 0;
   const unsigned grid = (unsigned)std::min<long>(tiles, 4096);
+  // the tile's 64 KB rule leaves out the source table, and CT = 8 tiles go up to the 160 KB cap:
+  // beyond 64 KB of dynamic LDS the kernel needs the attribute
+  FISDF_TRY(func_max_lds((const void*)kmesh_y_kernel, 160 * 1024));
   hipLaunchKernelGGL(kmesh_y_kernel, dim3(grid), dim3(256), lds, s, FX, ncol, nk,
                      kmesh[0], kmesh[1], kmesh[2], d_qs, nq, m, yT, qs, Is, goff, CT, half ? 1 : 0, mon);
   FISDF_HIP(hipGetLastError());
@@ -1687,8 +1721,7 @@ static int yf_launch(hipStream_t s, const int kmesh[3], const cplx* XT, int nip,
     *handled = true;                                                                           \
     return 0;                                                                                  \
   }
-  FISDF_YF(1, 1, 1) FISDF_YF(1, 1, 2) FISDF_YF(2, 2, 2) FISDF_YF(3, 3, 1) FISDF_YF(3, 3, 3)
-  FISDF_YF(4, 4, 4) FISDF_YF(2, 2, 1) FISDF_YF(1, 2, 2) FISDF_YF(4, 4, 1) FISDF_YF(2, 2, 4)
+  FISDF_KM_REG_MESHES(FISDF_YF)
 #undef FISDF_YF
   return 0;
 }
@@ -1705,7 +1738,8 @@ int y_fused(hipStream_t s, const cplx* X, int nip, int nao, const cplx* F, long 
   size_t lds = 0;
   bool ok = false;
   FISDF_TRY(yf_setup(kmesh, nao, h_qs, nq, &plan, &qmask, &lds, &ok));
-  if (!ok) return 0;
+  // no instantiation for this k-mesh: nothing is enqueued (the copies below used to run first)
+  if (!ok || kmesh_route(kmesh, 1).route != KM_REG) return 0;
   // mu-major copies of the plan's k: XT [slot][mu][I], FT [slot][mu][g]
   const int nsl = plan.nA + plan.nB;
   FISDF_CHECK(work && work_bytes >= sizeof(cplx) * (size_t)nsl * nao * ((size_t)nip + m),
@@ -1726,18 +1760,28 @@ int y_fused(hipStream_t s, const cplx* X, int nip, int nao, const cplx* F, long 
 }
 
 bool y_fused_applies(const int kmesh[3], int nao) {
-  static const int inst[][3] = {{1, 1, 1}, {1, 1, 2}, {2, 2, 2}, {3, 3, 1}, {3, 3, 3},
-                                {4, 4, 4}, {2, 2, 1}, {1, 2, 2}, {4, 4, 1}, {2, 2, 4}};
-  bool have = false;  // the instantiations yf_launch dispatches to
-  for (const auto& k : inst) have |= k[0] == kmesh[0] && k[1] == kmesh[1] && k[2] == kmesh[2];
-  if (!have) return false;
+  YFusedPlan p;
+  y_fused_plan(kmesh, nao, &p);
+  return p.applies;
+}
+
+void y_fused_plan(const int kmesh[3], int nao, YFusedPlan* out) {
+  *out = YFusedPlan{};
+  // the instantiations yf_launch dispatches to: the register list
+  if (nao < 1 || kmesh_route(kmesh, 1).route != KM_REG) return;
   YfPlan plan;
   unsigned long long qmask = 0;
   size_t lds = 0;
   bool ok = false;
   const int q0 = 0;
-  if (yf_setup(kmesh, nao, &q0, 1, &plan, &qmask, &lds, &ok) != 0) return false;
-  return ok;
+  if (yf_setup(kmesh, nao, &q0, 1, &plan, &qmask, &lds, &ok) != 0 || !ok) return;
+  out->applies = true;
+  out->nA = plan.nA;
+  out->nB = plan.nB;
+  for (int i = 0; i < plan.nA; ++i) out->kA[i] = plan.kA[i];
+  for (int i = 0; i < plan.nB; ++i) out->kB[i] = plan.kB[i];
+  out->lds = lds;
+  out->nkc = (nao + 4 * YF_MAXKS - 1) / (4 * YF_MAXKS);
 }
 
 int y_fused_stream(hipStream_t s, const cplx* x0, int ng0, int nao, const int* piv,
@@ -1755,6 +1799,7 @@ int y_fused_stream(hipStream_t s, const cplx* x0, int ng0, int nao, const int* p
   bool ok = false;
   FISDF_TRY(yf_setup(kmesh, nao, h_qs, nq, &plan, &qmask, &lds, &ok));
   if (!ok) return 0;
+  FISDF_CHECK(kmesh_route(kmesh, 1).route == KM_REG, "y_fused_stream: no kernel for this k-mesh");
   const int nsl = plan.nA + plan.nB;
   FISDF_CHECK(work && work_bytes >= sizeof(cplx) * (size_t)nsl * nao * ((size_t)nip + m),
               "y_fused_stream: workspace too small");

@@ -116,6 +116,17 @@ _SIGS = {
     "fisdf_conj_transpose": ([_vp, _vp, _i, _l, _vp, _i], _i),
     "fisdf_factor_plan": ([_i, _i, _i, _l, _ip, _ip, _ip, _ip, _ip, _i, C.POINTER(_l), _ip, _ip],
                           _i),
+    # the k-mesh transforms piece by piece
+    "fisdf_kmesh_plan": ([_ip, _l, _i, _i, _i, C.POINTER(_l), _ip, _ip, _i, _ip, _ip, _ip,
+                          C.POINTER(_l)], _i),
+    "fisdf_kmesh_y_ex": ([_vp, _vp, _l, _ip, _ip, _i, _i, _vp, _l, _l, _l, _i, _i, _dp, _ip], _i),
+    "fisdf_y_fused_ex": ([_vp, _vp, _i, _i, _vp, _l, _i, _ip, _ip, _i, _vp, _l, _l, _l,
+                          C.c_ulonglong, _ip], _i),
+    "fisdf_y_fused_stream_ex": ([_vp, _vp, _i, _i, _ip, _i, _i, _vp, _l, _i, _ip, _ip, _i, _vp, _l,
+                                 _l, _l, C.c_ulonglong, _i, _ip, _ip], _i),
+    "fisdf_k_wsrho_ex": ([_vp, _vp, _l, _ip, _dp, _vp, _l, _i, _dp, _ip], _i),
+    "fisdf_bloch_dft_ex": ([_vp, _vp, _l, _ip, _vp, _ip], _i),
+    "fisdf_bloch_band_ex": ([_vp, _vp, _l, _i, _vp, _i, _vp], _i),
     # composite entries
     "fisdf_build_opts_default": ([_vp], None),
     "fisdf_build": ([_vp, _vp, _i, _vp, _i, _ip, _ip, _dp, _vp, _ip], _i),

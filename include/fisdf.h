@@ -663,6 +663,63 @@ int fisdf_factor_plan(int n, int ncol, int batch, long work_elems, int* h_pchol_
                       int* h_pchol_nb, int* h_nblk, int* h_s0, int* h_rows, int rows_cap,
                       long* h_split_work_elems, int* h_sel_rpt, int* h_sel_nb);
 
+/* ---- the separable k-mesh transforms piece by piece (the y build, x4, get_k's pair, the Bloch
+ * AO), for tests of their dispatch.  Every pointer named d_ is device memory, every call with a
+ * context is synchronous and fails before it launches or copies anything when it cannot run, its
+ * output left as it was. ---- */
+/* what the k-mesh transforms do for a k-mesh (axes >= 1), from the host functions their launchers
+ * use (no context, no device).  h_route (3): the route of a transform over ncol columns (0 the
+ * register kernels: a k-mesh of the compiled list, ncol < 2^31; 1 the LDS kernel; 2 refused: an
+ * axis above 16, more than 160 KB of LDS or 2^31 tiles), then the LDS kernel's columns per tile
+ * (64, 32, 16 or 8) and its dynamic LDS bytes (both 0 on route 0 or with an axis above 16).
+ * *h_half_count: the k stored under time reversal (k <= -k); h_runs (runs_cap pairs) / *h_nruns:
+ * those k as [begin, end) runs.  h_fused (4): whether the fused y kernel takes (kmesh, nao), its
+ * chunk A and chunk B slot counts and its K chunks of 28 per slot (all 0 when it does not);
+ * h_slots (48): the k of every slot, chunk A's then chunk B's, -1 beyond; h_fused_bytes (2): the
+ * fused kernel's dynamic LDS bytes and the workspace bytes y_fused asks for (nip, nao, m).  Any
+ * output may be NULL */
+int fisdf_kmesh_plan(const int kmesh[3], long ncol, int nao, int nip, int m, long* h_route,
+                     int* h_half_count, int* h_runs, int runs_cap, int* h_nruns, int* h_fused,
+                     int* h_slots, long* h_fused_bytes);
+/* y_q = Phi^T (Re(Phi FX))^2 for the ascending q-list h_qs (nq entries; uploaded by the call):
+ * d_FX (nk rows of ncol columns; half: only the rows of the k <= -k, the others taken as
+ * conj(FX[-k])), column c = I * m + g written to d_yT[slot * qs + I * Is + goff + g] (conj_out:
+ * conjugated; register route only).  *h_mon = max |Im(Phi FX)|, *h_route as h_route[0] of
+ * fisdf_kmesh_plan (-1: nothing ran) */
+int fisdf_kmesh_y_ex(fisdf_ctx* ctx, const void* d_FX, long ncol, const int kmesh[3],
+                     const int* h_qs, int nq, int m, void* d_yT, long qs, long Is, long goff,
+                     int half, int conj_out, double* h_mon, int* h_route);
+/* the fused y build under time reversal: d_X (nk, nip, nao), d_F (k stride fks, m rows of nao),
+ * rmask: the q (bits) stored as doubles in the first half of their slot (bits outside the q-list
+ * are ignored).  *h_handled = 0: the fused kernel does not take (kmesh, nao); nothing was written.
+ * The workspace comes from the context */
+int fisdf_y_fused_ex(fisdf_ctx* ctx, const void* d_X, int nip, int nao, const void* d_F, long fks,
+                     int m, const int kmesh[3], const int* h_qs, int nq, void* d_yT, long qs,
+                     long Is, long goff, unsigned long long rmask, int* h_handled);
+/* the same, streamed: rows [0, nip) of y in blocks of `rows` (a multiple of 16, 16..1024), block
+ * rows gathered from d_x0 (nk, ng0, nao) through h_piv (nip entries in [0, ng0)); two_streams: odd
+ * blocks on a second stream.  The progress word is set to done on the context's stream before the
+ * first launch.  *h_err: the device flag of a wait past its bound */
+int fisdf_y_fused_stream_ex(fisdf_ctx* ctx, const void* d_x0, int ng0, int nao, const int* h_piv,
+                            int nip, int rows, const void* d_F, long fks, int m,
+                            const int kmesh[3], const int* h_qs, int nq, void* d_yT, long qs,
+                            long Is, long goff, unsigned long long rmask, int two_streams,
+                            int* h_handled, int* h_err);
+/* get_k's pair in place on d_B (nk rows of ncol columns): rho_s = Phi rho_k, V_s = W_s Re(rho_s)
+ * (d_Ws: doubles, row s at s * ws_Rstride), V_k = Phi^T V_s.  use_reg = 1: the register kernel
+ * where the k-mesh has one (*h_handled = 1), else, and with use_reg = 0, the two dense Phi GEMMs
+ * (Phi from the lattice h_a).  *h_mon = max |Im rho_s| */
+int fisdf_k_wsrho_ex(fisdf_ctx* ctx, void* d_B, long ncol, const int kmesh[3], const double h_a[9],
+                     const void* d_Ws, long ws_Rstride, int use_reg, double* h_mon,
+                     int* h_handled);
+/* the tail of fisdf_eval_ao: d_chi[k][c] = sum_R exp(2 pi i sum_a r_a k_a / n_a) d_F[R][c] (d_F
+ * doubles, nk rows of ncol); *h_route: 0 the register kernel, 1 one thread per (k, column) */
+int fisdf_bloch_dft_ex(fisdf_ctx* ctx, const void* d_F, long ncol, const int kmesh[3], void* d_chi,
+                       int* h_route);
+/* the tail of fisdf_eval_ao_band: d_chi[k][c] = sum_t d_ph[t * nkb + k] d_F[t][c], t < nT */
+int fisdf_bloch_band_ex(fisdf_ctx* ctx, const void* d_F, long ncol, int nT, const void* d_ph,
+                        int nkb, void* d_chi);
+
 #ifdef __cplusplus
 }
 #endif
