@@ -466,10 +466,36 @@ int free_factors(fisdf_ctx* c) {
 // x2 = sum_{q in [q0,q1)} conj(x0_q) x0_q^T, via P = x0 permuted to (ng0, nq*nao) and the
 // Hermitian update P P^H (only its real part is used: Re(P P^H) = Re(conj(P) P^T)).
 // `tmp` must hold ng0*nq*nao complex.
+// the HERK split-K of the selection Gram (n x n from K columns): more tiles in flight while the
+// triangle alone leaves CUs idle and every part keeps 256 columns
+int select_gram_ksplit(int ng0, int K) {
+  int ks = 1;
+  const long tiles = (long)((ng0 + 63) / 64) * ((ng0 + 63) / 64 + 1) / 2;
+  while (tiles * ks < 512 && K / (ks * 2) >= 256) ks *= 2;
+  return ks;
+}
+
+// info (nullable, 3 ints): the k-points summed (the representatives under the fold), the permute
+// launches and the HERK split-K
+void select_gram_plan(const int* kmesh, bool fold, int nq, int ng0, int nao, int* info) {
+  int launches = nq > 0 ? 1 : 0;
+  if (kmesh && fold) {
+    std::vector<int> reps;
+    std::vector<char> self;
+    kmesh_reps(kmesh, &reps, &self);
+    nq = (int)reps.size();
+    launches = (nq + 63) / 64;
+  }
+  info[0] = nq;
+  info[1] = launches;
+  info[2] = nq > 0 ? select_gram_ksplit(ng0, nq * nao) : 0;
+}
+
+// fold: sum the time-reversal representatives of `kmesh` only (the whole mesh, q0 = 0, q1 = nk)
 int select_gram(fisdf_ctx* c, const cplx* x0, int nk, int q0, int q1, int ng0, int nao, cplx* x2,
-                cplx* tmp, const int* kmesh) {
+                cplx* tmp, const int* kmesh, bool fold) {
   int nq = q1 - q0;
-  if (kmesh && c->time_reversal && q0 == 0 && q1 == nk) {
+  if (kmesh && fold && q0 == 0 && q1 == nk) {
     // time reversal (x0_{-q} = conj(x0_q)): Re(x0_{-q} x0_{-q}^H) = Re(x0_q x0_q^H), so the sum
     // over the k-mesh is the sum over the representatives q <= -q with a paired one counted
     // twice — its copy scaled by sqrt(2): 36 of 64 k at 4x4x4
@@ -484,9 +510,7 @@ int select_gram(fisdf_ctx* c, const cplx* x0, int nk, int q0, int q1, int ng0, i
     FISDF_TRY(permute_kgm(c->stream, x0 + (long)q0 * ng0 * nao, nq, ng0, nao, tmp));
   }
   const int K = nq * nao;
-  int ks = 1;
-  const long tiles = (long)((ng0 + 63) / 64) * ((ng0 + 63) / 64 + 1) / 2;
-  while (tiles * ks < 512 && K / (ks * 2) >= 256) ks *= 2;
+  const int ks = select_gram_ksplit(ng0, K);
   void* work = nullptr;
   if (ks > 1) FISDF_TRY(devbuf_get(c->ws_main, sizeof(cplx) * (size_t)ks * ng0 * ng0, &work));
   // only Re(x2) enters the selection (fftisdf.py:379): real-part HERK, imaginary part zero
@@ -1475,13 +1499,23 @@ static int ystream_arm(fisdf_ctx* c, const void* x0, int ng0, const void* f, lon
   return 0;
 }
 
+// The selection's work area: the n x n complex x4 of the generic path, which also holds the
+// co-resident kernels' scratch (their plans check it against n*n doubles) and the register panels'
+// n*n + 17 n + 1 doubles (pchol_select_real) — the larger below n = 18, where a work area of n*n
+// complex let the panels' L panel and diagonal run over the pivots and the rank behind it
+static size_t select_work_bytes(int n) {
+  const size_t nn = (size_t)n * n;
+  return std::max(sizeof(cplx) * nn, sizeof(double) * (nn + 17 * (size_t)n + 1));
+}
+
 // The selection's pivots on the device: the cooperative kernel, the blocked or the generic pivoted
 // Cholesky (in that order of preference), then ONE pinned read-back of {error flag, rank, pivots}
 // and one stream synchronisation (round 2 synchronised twice through pageable copies); a
 // cooperative run that reports a stalled step is redone on the non-cooperative paths.
 static int select_pivots_dev(fisdf_ctx* c, const cplx* X2, double scale, int ng0, int nip_max,
                              double tol, cplx* X4, int* piv, int* rank, cplx* L, double* d,
-                             int* flags, double* w, int* h_perm, int* h_rank) {
+                             int* flags, double* w, int* h_perm, int* h_rank,
+                             const SelOpts* opt = nullptr, int* h_info = nullptr) {
   const size_t nint = 2 + (size_t)nip_max;
   if (c->sel_cap < nint) {
     if (c->sel_pinned) FISDF_HIP(hipHostFree(c->sel_pinned));
@@ -1510,8 +1544,10 @@ static int select_pivots_dev(fisdf_ctx* c, const cplx* X2, double scale, int ng0
       FISDF_HIP(hipEventRecord(c->ev_ysfork, c->stream));
     }
     bool publishes = false;
+    SelRan ran = {};
     FISDF_TRY(pchol_select_real(c->stream, X2, scale, ng0, nip_max, tol, piv, rank, (double*)X4,
-                                flags, &handled, pass == 0, &coop_err, progress, &publishes));
+                                flags, &handled, pass == 0, &coop_err, progress, &publishes, opt,
+                                &ran));
     if (stream_y) {
       // whatever ran, consumers waiting on the progress word are released when it has ended
       FISDF_HIP(hipMemsetD32Async(c->ys_dev, kSelDone, 1, c->stream));
@@ -1523,6 +1559,8 @@ static int select_pivots_dev(fisdf_ctx* c, const cplx* X2, double scale, int ng0
       FISDF_TRY(devbuf_get(c->ws_main, sizeof(cplx) * pchol_trail_elems(ng0, 1), &trail));
       FISDF_TRY(pchol(c->stream, X4, ng0, 0, ng0, 1, nip_max, tol, 0.0, L, piv, rank, d, flags, w,
                       (cplx*)trail));
+      const bool blk = pchol_path(ng0) == PCHOL_BLOCKED;
+      ran = SelRan{blk ? SEL_RAN_PCHOL_BLOCKED : SEL_RAN_PCHOL_STEP, 0, 0, blk ? PCHOL_NB : 0, 0};
     }
     int* hp = c->sel_pinned;
     hp[0] = 0;
@@ -1534,7 +1572,13 @@ static int select_pivots_dev(fisdf_ctx* c, const cplx* X2, double scale, int ng0
     if (stream_y && hp[0] != 0) c->ys.stale = true;
     if (hp[0] == 0) {
       *h_rank = hp[1];
-      std::memcpy(h_perm, hp + 2, sizeof(int) * nip_max);
+      // the _ex entry (h_info) receives the rank's pivots only: what lies beyond is the caller's
+      const int ncopy = h_info ? std::max(0, std::min(hp[1], nip_max)) : nip_max;
+      std::memcpy(h_perm, hp + 2, sizeof(int) * ncopy);
+      if (h_info) {
+        const int v[6] = {ran.kernel, ran.G, ran.RW, ran.K, ran.tpr, pass + 1};
+        std::memcpy(h_info, v, sizeof(v));
+      }
       return 0;
     }
   }
@@ -1570,7 +1614,7 @@ static int select_points_impl(fisdf_ctx* c, const void* x0v, int nk, const int* 
   const cplx* x0 = (const cplx*)x0v;
   Carver cv;
   size_t oX2 = cv.take(sizeof(cplx) * (size_t)ng0 * ng0);
-  size_t oX4 = cv.take(sizeof(cplx) * (size_t)ng0 * ng0);
+  size_t oX4 = cv.take(select_work_bytes(ng0));
   size_t oPm = cv.take(sizeof(cplx) * (size_t)ng0 * nk * nao);
   size_t oL = cv.take(sizeof(cplx) * (size_t)ng0 * nip_max);
   size_t oP = cv.take(sizeof(int) * nip_max);
@@ -1585,7 +1629,8 @@ static int select_points_impl(fisdf_ctx* c, const void* x0v, int nk, const int* 
   cplx* X4 = (cplx*)(b + oX4);
   // x2 = sum_q conj(x0_q) x0_q^T   (fftisdf.py:376-378; real part taken below) as one
   // K = nk*nao Hermitian rank-K update of the permuted x0
-  FISDF_TRY(select_gram(c, x0, nk, 0, nk, ng0, nao, X2, (cplx*)(b + oPm), kmesh));
+  FISDF_TRY(select_gram(c, x0, nk, 0, nk, ng0, nao, X2, (cplx*)(b + oPm), kmesh,
+                        c->time_reversal != 0));
   // x4 = Re(x2)^2 / nk (:379) and the greedy pivoted Cholesky (:381-384), first nip_max
   // pivots: real blocked panels (X4's storage holds the real trailing matrix)
   int rank = 0;
@@ -1608,7 +1653,102 @@ int fisdf_select_gram(fisdf_ctx* c, const void* x0, int nk, int q0, int q1, int 
   }
   void* base;
   FISDF_TRY(arena_get(c, sizeof(cplx) * (size_t)ng0 * (q1 - q0) * nao, &base));
-  return select_gram(c, (const cplx*)x0, nk, q0, q1, ng0, nao, (cplx*)x2, (cplx*)base, nullptr);
+  return select_gram(c, (const cplx*)x0, nk, q0, q1, ng0, nao, (cplx*)x2, (cplx*)base, nullptr,
+                     false);
+}
+
+static int select_gram_plan_checked(const int* kmesh, int fold, int nk, int q0, int q1, int ng0,
+                                    int nao, int* h_info) {
+  FISDF_CHECK(h_info && nk > 0 && 0 <= q0 && q0 <= q1 && q1 <= nk && ng0 > 0 && nao > 0,
+              "select_gram_plan: bad sizes");
+  FISDF_CHECK(!kmesh || (kmesh[0] > 0 && kmesh[1] > 0 && kmesh[2] > 0 &&
+                         (long)kmesh[0] * kmesh[1] * kmesh[2] == nk),
+              "select_gram_plan: the k-mesh does not have nk points");
+  FISDF_CHECK(!fold || (kmesh && q0 == 0 && q1 == nk),
+              "select_gram_plan: the fold needs the k-mesh and the whole of it");
+  select_gram_plan(kmesh, fold != 0, q1 - q0, ng0, nao, h_info);
+  return 0;
+}
+
+int fisdf_select_gram_plan(const int* kmesh, int fold, int nk, int q0, int q1, int ng0, int nao,
+                           int* h_info) {
+  t_cur_ctx = nullptr;
+  return select_gram_plan_checked(kmesh, fold, nk, q0, q1, ng0, nao, h_info);
+}
+
+int fisdf_select_gram_ex(fisdf_ctx* c, const void* x0, const int* kmesh, int fold, int nk, int q0,
+                         int q1, int ng0, int nao, void* x2, int* h_info) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(x0 && x2, "select_gram_ex: null argument");
+  int info[3];
+  FISDF_TRY(select_gram_plan_checked(kmesh, fold, nk, q0, q1, ng0, nao, info));
+  if (q1 == q0) {
+    FISDF_HIP(hipMemsetAsync(x2, 0, sizeof(cplx) * (size_t)ng0 * ng0, c->stream));
+  } else {
+    void* base;
+    FISDF_TRY(arena_get(c, sizeof(cplx) * (size_t)ng0 * (q1 - q0) * nao, &base));
+    FISDF_TRY(select_gram(c, (const cplx*)x0, nk, q0, q1, ng0, nao, (cplx*)x2, (cplx*)base, kmesh,
+                          fold != 0));
+  }
+  FISDF_HIP(hipStreamSynchronize(c->stream));
+  if (h_info) std::memcpy(h_info, info, sizeof(info));
+  return 0;
+}
+
+int fisdf_select_plan(int n, int rmax, int ncu, int lds_cols, int wgs, int* h_mode, int* h_batch,
+                      long* h_batch_lds, int* h_coop, long* h_coop_lds, int* h_panel,
+                      int* h_pchol_path) {
+  t_cur_ctx = nullptr;
+  FISDF_CHECK(n >= 1 && rmax >= 1 && rmax <= n && ncu >= 0 && lds_cols >= 0 && wgs >= 0,
+              "select_plan: bad sizes");
+  SelBatchPlan bp;
+  SelCoopPlan cp;
+  select_batch_plan(n, rmax, ncu, &bp);
+  select_coop_plan(n, rmax, ncu, lds_cols, wgs, &cp);
+  if (h_mode) *h_mode = select_default_mode(rmax);
+  if (h_batch) {
+    const int v[4] = {bp.ok, bp.why, bp.grid, bp.RW};
+    std::memcpy(h_batch, v, sizeof(v));
+  }
+  if (h_batch_lds) *h_batch_lds = bp.lds;
+  if (h_coop) {
+    const int v[7] = {cp.ok, cp.why, cp.split, cp.G, cp.RW, cp.K, cp.tpr};
+    std::memcpy(h_coop, v, sizeof(v));
+  }
+  if (h_coop_lds) *h_coop_lds = cp.lds;
+  if (h_panel) pchol_real_variant(n, h_panel, h_panel + 1);
+  if (h_pchol_path) *h_pchol_path = pchol_path(n);
+  return 0;
+}
+
+int fisdf_select_pivots_ex(fisdf_ctx* c, const void* x2, int nk, int ng0, int nip_max, double tol,
+                           int mode, int lds_cols, int wgs, int* h_perm, int* h_npiv,
+                           int* h_full_rank, int* h_info) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(x2 && h_perm && h_npiv && h_info, "select_pivots_ex: null argument");
+  FISDF_CHECK(nk > 0 && ng0 > 0 && nip_max > 0 && nip_max <= ng0, "select_pivots_ex: bad sizes");
+  FISDF_CHECK(mode >= -1 && mode <= 2 && lds_cols >= 0 && wgs >= 0,
+              "select_pivots_ex: mode is -1..2, lds_cols and wgs are 0 or positive");
+  StageTimer tm(c, FISDF_ST_SELECT);
+  Carver cv;
+  size_t oX4 = cv.take(select_work_bytes(ng0));
+  size_t oL = cv.take(sizeof(cplx) * (size_t)ng0 * nip_max);
+  size_t oP = cv.take(sizeof(int) * nip_max);
+  size_t oR = cv.take(sizeof(int) * 4);
+  size_t oD = cv.take(sizeof(double) * ng0);
+  size_t oF = cv.take(sizeof(int) * 4);
+  size_t oW = cv.take(sizeof(double) * (1 + nip_max));
+  void* base;
+  FISDF_TRY(arena_get(c, cv.off, &base));
+  char* b = (char*)base;
+  const SelOpts opt = {mode, lds_cols, wgs};
+  int rank = 0;
+  FISDF_TRY(select_pivots_dev(c, (const cplx*)x2, 1.0 / nk, ng0, nip_max, tol, (cplx*)(b + oX4),
+                              (int*)(b + oP), (int*)(b + oR), (cplx*)(b + oL), (double*)(b + oD),
+                              (int*)(b + oF), (double*)(b + oW), h_perm, &rank, &opt, h_info));
+  *h_npiv = rank;
+  if (h_full_rank) *h_full_rank = rank < nip_max ? 1 : 0;
+  return 0;
 }
 
 int fisdf_select_pivots(fisdf_ctx* c, const void* x2, int nk, int ng0, int nip_max, double tol,
@@ -1618,7 +1758,7 @@ int fisdf_select_pivots(fisdf_ctx* c, const void* x2, int nk, int ng0, int nip_m
   nip_max = std::min(nip_max, ng0);
   StageTimer tm(c, FISDF_ST_SELECT);
   Carver cv;
-  size_t oX4 = cv.take(sizeof(cplx) * (size_t)ng0 * ng0);
+  size_t oX4 = cv.take(select_work_bytes(ng0));
   size_t oL = cv.take(sizeof(cplx) * (size_t)ng0 * nip_max);
   size_t oP = cv.take(sizeof(int) * nip_max);
   size_t oR = cv.take(sizeof(int) * 4);

@@ -166,10 +166,55 @@ int chol_unpivoted(hipStream_t s, cplx* W, int n, int batch, double tol_rel, int
 bool coop_launch_enabled();
 constexpr int kSelPublish = 16;
 constexpr int kSelDone = 1 << 30;
+// What the selection's launchers do for given sizes: the host arithmetic of
+// pchol_select_batch_launch and pchol_select_coop_launch, which call these themselves.  `why` says
+// which rule refused a kernel, in the order the launcher checks them.
+enum SelKernel {
+  SEL_RAN_BATCH = 0, SEL_RAN_COOP = 1, SEL_RAN_COOP_SPLIT = 2, SEL_RAN_PANEL = 3,
+  SEL_RAN_PCHOL_BLOCKED = 4, SEL_RAN_PCHOL_STEP = 5
+};
+enum SelBatchWhy {
+  SELB_OK = 0, SELB_N_SMALL = 1, SELB_N_LARGE = 2, SELB_RMAX = 3, SELB_GRID = 4, SELB_LDS = 5,
+  SELB_SCRATCH = 6
+};
+enum SelCoopWhy {
+  SELC_OK = 0, SELC_N_SMALL = 1, SELC_NO_GRID = 2, SELC_K_SMALL = 3, SELC_LDS = 4, SELC_ROWS = 5,
+  SELC_SCRATCH = 6
+};
+struct SelBatchPlan {
+  int ok, why;
+  int grid;  // owners + the leader
+  int RW;    // rows per owner
+  long lds;  // dynamic LDS bytes
+};
+struct SelCoopPlan {
+  int ok, why, split;
+  int G, RW, K, tpr;
+  long lds;
+};
+// ncu: the device's CU count
+void select_batch_plan(int n, int rmax, int ncu, SelBatchPlan* p);
+// lds_cols > 0: the split form with at most that many columns of the owned L rows in LDS
+// (FISDF_SEL_LDS_COLS); wgs > 0: the grid's cap instead of 128 (FISDF_SEL_WGS)
+void select_coop_plan(int n, int rmax, int ncu, int lds_cols, int wgs, SelCoopPlan* p);
+// 0 batch, 1 coop: the kernel tried first for rmax pivots when no switch is set
+int select_default_mode(int rmax);
+
+// opt (nullable): the mode (-1: the default rule and FISDF_SEL_MODE, 0 batch, 1 coop, 2 blocked)
+// and the two sizes above given by the caller, the environment's then unread (lds_cols, wgs: 0 =
+// the production value).  ran (nullable) receives what was enqueued when *handled.
+struct SelOpts {
+  int mode, lds_cols, wgs;
+};
+struct SelRan {
+  int kernel;  // SelKernel
+  int G, RW, K, tpr;
+};
 int pchol_select_real(hipStream_t s, const cplx* X2, double scale, int n, int rmax, double tol,
                       int* piv, int* rank, double* work, int* flags, bool* handled,
                       bool allow_coop, const int** coop_err, int* progress = nullptr,
-                      bool* publishes = nullptr);
+                      bool* publishes = nullptr, const SelOpts* opt = nullptr,
+                      SelRan* ran = nullptr);
 
 // Where plane i0 of input row r lives when the rows arrive in grid slices (the all-to-all
 // pieces of a k-sharded build): in + base + r * ld, one entry per plane (device table)

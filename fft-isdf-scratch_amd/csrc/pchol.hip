@@ -1515,16 +1515,56 @@ hipError_t launch_coresident(const void* fn, int grid, int threads, void** args,
   return hipLaunchKernel(fn, dim3(grid), dim3(threads), args, lds, s);
 }
 
+constexpr size_t kSelLds = 150 * 1024;  // dynamic LDS of a selection workgroup at most
+
+// the cooperative kernel's grid and LDS split (see pchol_select_coop_launch)
+void select_coop_plan(int n, int rmax, int ncu, int lds_cols, int wgs, SelCoopPlan* p) {
+  *p = SelCoopPlan{};
+  auto refuse = [&](int why) { p->ok = 0; p->why = why; };
+  if (n < 64) return refuse(SELC_N_SMALL);
+  // 128 workgroups: the per-pivot time is flat from 128 to 256 (cross-XCD round trips)
+  int G = std::min({wgs > 0 ? wgs : 128, ncu, (n + 7) / 8});
+  if (G < 1) return refuse(SELC_NO_GRID);
+  int RW = (n + G - 1) / G;
+  G = (n + RW - 1) / RW;
+  int K = rmax, tpr = 8;
+  size_t lds = sizeof(double) * ((size_t)RW * rmax + rmax + 2 * (size_t)RW);
+  if (lds > kSelLds || lds_cols > 0) {
+    // the owned L rows do not fit: one workgroup per CU, the first K columns in LDS and the
+    // rest read back (agent-coherent) from the global L
+    p->split = 1;
+    G = std::min(ncu, (n + 7) / 8);
+    RW = (n + G - 1) / G;
+    G = (n + RW - 1) / RW;
+    K = (int)(((long)(kSelLds / sizeof(double)) - rmax - 2L * RW) / RW);
+    if (lds_cols > 0) K = std::min(K, lds_cols);
+    p->G = G; p->RW = RW; p->K = K;
+    if (K < 16) return refuse(SELC_K_SMALL);
+    K = std::min(K, rmax);
+    tpr = 8;
+    lds = sizeof(double) * ((size_t)RW * K + rmax + 2 * (size_t)RW);
+  }
+  p->G = G; p->RW = RW; p->K = K; p->lds = (long)lds;
+  if (lds > kSelLds) return refuse(SELC_LDS);
+  if (RW > SC_MAXRW) return refuse(SELC_ROWS);
+  // threads per owned row: the most (a power of two, <= 32) that the workgroup holds
+  while (tpr < 32 && RW * tpr * 2 <= SC_THREADS) tpr *= 2;
+  p->tpr = tpr;
+  // scratch in the caller's work area (n*n doubles): records, global L, error flag
+  if ((long)(4 * G + (long)n * rmax + 2) > (long)n * n) return refuse(SELC_SCRATCH);
+  p->ok = 1;
+}
+
 // launches pchol_select_coop when the owned L rows fit the LDS of a co-resident grid;
 // *handled = false (nothing enqueued that matters) otherwise or if the launch is refused.  No
 // host synchronisation: *err_dev receives the device address of the kernel's error flag (a
 // stalled step), which the caller reads back with the pivots and the rank in one copy.
 int pchol_select_coop_launch(hipStream_t s, const cplx* X2, double scale, int n, int rmax,
                              double tol, int* piv, int* rank, double* work, bool* handled,
-                             const int** err_dev, int* progress) {
+                             const int** err_dev, int* progress, const SelOpts* opt, SelRan* ran) {
   *handled = false;
   *err_dev = nullptr;
-  if (!select_coop_enabled() || n < 64) return 0;
+  if ((!opt && !select_coop_enabled()) || n < 64) return 0;
   static const int ncu = [] {
     int dev = 0, v = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -1534,39 +1574,21 @@ int pchol_select_coop_launch(hipStream_t s, const cplx* X2, double scale, int n,
   }();
   // read per call (the GPU tests force the split path on small cases): FISDF_SEL_LDS_COLS=k
   // keeps at most k columns of the owned L rows in LDS
-  const char* ek = getenv("FISDF_SEL_LDS_COLS");
-  const int kcap = ek ? atoi(ek) : 0;
-  constexpr size_t kLds = 150 * 1024;
-  // 128 workgroups: the per-pivot time is flat from 128 to 256 (cross-XCD round trips)
+  const char* ek = opt ? nullptr : getenv("FISDF_SEL_LDS_COLS");
+  const int kcap = opt ? opt->lds_cols : (ek ? atoi(ek) : 0);
+  constexpr size_t kLds = kSelLds;
   // FISDF_SEL_WGS=g caps the grid (experiments: the exchange's cost against its poller count)
-  const char* eg = getenv("FISDF_SEL_WGS");
-  int G = std::min({eg ? std::max(1, atoi(eg)) : 128, ncu, (n + 7) / 8});
-  if (G < 1) return 0;
-  int RW = (n + G - 1) / G;
-  G = (n + RW - 1) / RW;
-  int K = rmax, tpr = 8;
-  size_t lds = sizeof(double) * ((size_t)RW * rmax + rmax + 2 * (size_t)RW);
-  if (lds > kLds || kcap > 0) {
-    // the owned L rows do not fit: one workgroup per CU, the first K columns in LDS and the
-    // rest read back (agent-coherent) from the global L
-    G = std::min(ncu, (n + 7) / 8);
-    RW = (n + G - 1) / G;
-    G = (n + RW - 1) / RW;
-    K = (int)(((long)(kLds / sizeof(double)) - rmax - 2L * RW) / RW);
-    if (kcap > 0) K = std::min(K, kcap);
-    if (K < 16) return 0;
-    K = std::min(K, rmax);
-    tpr = 8;
-    lds = sizeof(double) * ((size_t)RW * K + rmax + 2 * (size_t)RW);
-  }
-  if (lds > kLds || RW > SC_MAXRW) return 0;
-  // threads per owned row: the most (a power of two, <= 32) that the workgroup holds
-  while (tpr < 32 && RW * tpr * 2 <= SC_THREADS) tpr *= 2;
+  const char* eg = opt ? nullptr : getenv("FISDF_SEL_WGS");
+  const int wgs = opt ? opt->wgs : (eg ? std::max(1, atoi(eg)) : 0);
+  SelCoopPlan pl;
+  select_coop_plan(n, rmax, ncu, kcap, wgs, &pl);
+  if (!pl.ok) return 0;
+  int G = pl.G, RW = pl.RW, K = pl.K, tpr = pl.tpr;
+  const size_t lds = (size_t)pl.lds;
   // scratch in the caller's work area (n*n doubles): records, global L, error flag
   u32x4* rec = (u32x4*)work;
   double* Lg = work + 4 * G;
   int* err = (int*)(Lg + (long)n * rmax);
-  if ((long)(4 * G + (long)n * rmax + 2) > (long)n * n) return 0;
   FISDF_HIP(hipMemsetAsync(rec, 0, 2 * G * sizeof(u32x4), s));
   FISDF_HIP(hipMemsetAsync(err, 0, sizeof(int), s));
   FISDF_HIP(hipMemsetAsync(rank, 0, sizeof(int), s));
@@ -1593,6 +1615,7 @@ int pchol_select_coop_launch(hipStream_t s, const cplx* X2, double scale, int n,
   }
   *err_dev = err;
   *handled = true;
+  if (ran) *ran = SelRan{pl.split ? SEL_RAN_COOP_SPLIT : SEL_RAN_COOP, G, RW, K, tpr};
   if (profp) {
     std::vector<unsigned long long> h(4 * (size_t)rmax);
     FISDF_HIP(hipMemcpyAsync(h.data(), profp, sizeof(unsigned long long) * h.size(),
@@ -1622,23 +1645,47 @@ int pchol_select_coop_launch(hipStream_t s, const cplx* X2, double scale, int n,
 // "blocked" (or FISDF_SEL_COOP=0) runs the blocked single-CU path only.  Default: batch from
 // 800 pivots on (C4, 1000 pivots: 5.3 vs 6.4 ms), coop below (C3, 600: 4.36 vs 4.41 ms, a tie;
 // profiles/r05/selection/README.txt)
+int select_default_mode(int rmax) { return rmax >= 800 ? 0 : 1; }
+
 int select_mode(int rmax) {
   const char* e = getenv("FISDF_SEL_MODE");
   if (!select_coop_enabled()) return 2;
-  if (!e) return rmax >= 800 ? 0 : 1;
+  if (!e) return select_default_mode(rmax);
   if (!strcmp(e, "coop")) return 1;
   if (!strcmp(e, "blocked")) return 2;
   return 0;
 }
 
-// launches pchol_select_batch when the owned rows fit (n <= 4096, 16 rows per workgroup on at
-// most ncu - 1 workgroups, rmax <= 1024); *handled = false otherwise or if the launch is refused.
+// the batched kernel's grid and LDS (see pchol_select_batch_launch)
+void select_batch_plan(int n, int rmax, int ncu, SelBatchPlan* p) {
+  *p = SelBatchPlan{};
+  auto refuse = [&](int why) { p->ok = 0; p->why = why; };
+  if (n < 2 * SB_M) return refuse(SELB_N_SMALL);
+  if (n > SB_GR * SB_THREADS) return refuse(SELB_N_LARGE);
+  if (rmax > 4096) return refuse(SELB_RMAX);
+  const int RW = 16;
+  const int G = (n + RW - 1) / RW;
+  p->RW = RW;
+  p->grid = G + 1;
+  if (G + 1 > ncu) return refuse(SELB_GRID);
+  const size_t owner = sizeof(double) * (8 * 256 + SB_M * SB_S + 2 * 16 * SB_S + (size_t)RW * rmax);
+  const size_t leader = sizeof(double) * (3 * 8 * 256 + SB_M * SB_M + 64 + SB_M * SB_S + 16);
+  const size_t lds = std::max(owner, leader);
+  p->lds = (long)lds;
+  if (lds > kSelLds) return refuse(SELB_LDS);
+  // scratch in the caller's work area (n*n doubles): granules, publish area, global L, error flag
+  if (2L * n + 2L * SB_NPUB + (long)n * rmax + 2 > (long)n * n) return refuse(SELB_SCRATCH);
+  p->ok = 1;
+}
+
+// launches pchol_select_batch when select_batch_plan takes the sizes: 64 <= n <= 4096, 16 rows
+// per workgroup on at most ncu - 1 workgroups, the owner's LDS within 150 KB (rmax <= 1008) and
+// the scratch within the n*n work area; *handled = false otherwise or if the launch is refused.
 int pchol_select_batch_launch(hipStream_t s, const cplx* X2, double scale, int n, int rmax,
                               double tol, int* piv, int* rank, double* work, bool* handled,
-                              const int** err_dev) {
+                              const int** err_dev, SelRan* ran) {
   *handled = false;
   *err_dev = nullptr;
-  if (n < 2 * SB_M || n > SB_GR * SB_THREADS || rmax > 4096) return 0;
   static const int ncu = [] {
     int dev = 0, v = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -1646,21 +1693,19 @@ int pchol_select_batch_launch(hipStream_t s, const cplx* X2, double scale, int n
       return 0;
     return v;
   }();
-  const int RW = 16;
-  const int G = (n + RW - 1) / RW;
-  if (G + 1 > ncu) return 0;
-  constexpr size_t kLds = 150 * 1024;
-  const size_t owner = sizeof(double) * (8 * 256 + SB_M * SB_S + 2 * 16 * SB_S + (size_t)RW * rmax);
-  const size_t leader = sizeof(double) * (3 * 8 * 256 + SB_M * SB_M + 64 + SB_M * SB_S + 16);
-  const size_t lds = std::max(owner, leader);
-  if (lds > kLds) return 0;
+  SelBatchPlan pl;
+  select_batch_plan(n, rmax, ncu, &pl);
+  if (!pl.ok) return 0;
+  const int RW = pl.RW;
+  const int G = pl.grid - 1;
+  constexpr size_t kLds = kSelLds;
+  const size_t lds = (size_t)pl.lds;
   // scratch in the caller's work area (n*n doubles): granules, publish area, global L, error flag
   u32x4* ddg = (u32x4*)work;
   const long pub_d = 2L * SB_NPUB;
   u32x4* pub = (u32x4*)(work + 2L * n);
   double* Lg = work + 2L * n + pub_d;
   int* err = (int*)(Lg + (long)n * rmax);
-  if (2L * n + pub_d + (long)n * rmax + 2 > (long)n * n) return 0;
   FISDF_HIP(hipMemsetAsync(ddg, 0, sizeof(u32x4) * n, s));
   FISDF_HIP(hipMemsetAsync(pub, 0, sizeof(u32x4) * SB_NPUB, s));  // no stale batch words
   FISDF_HIP(hipMemsetAsync(err, 0, sizeof(int), s));
@@ -1689,6 +1734,7 @@ int pchol_select_batch_launch(hipStream_t s, const cplx* X2, double scale, int n
   }
   *err_dev = err;
   *handled = true;
+  if (ran) *ran = SelRan{SEL_RAN_BATCH, G + 1, RW, rmax, 0};
   if (profp) {
     std::vector<unsigned long long> h(4 * (size_t)nb_cap);
     FISDF_HIP(hipMemcpyAsync(h.data(), profp, sizeof(unsigned long long) * h.size(),
@@ -1735,20 +1781,21 @@ bool pchol_real_variant(int n, int* rpt, int* nb) {
 
 int pchol_select_real(hipStream_t s, const cplx* X2, double scale, int n, int rmax, double tol,
                       int* piv, int* rank, double* work, int* flags, bool* handled,
-                      bool allow_coop, const int** coop_err, int* progress, bool* publishes) {
+                      bool allow_coop, const int** coop_err, int* progress, bool* publishes,
+                      const SelOpts* opt, SelRan* ran) {
   *handled = false;
   *coop_err = nullptr;
   if (publishes) *publishes = false;
   if (rmax <= 0) return 0;
-  const int mode = select_mode(rmax);
+  const int mode = opt && opt->mode >= 0 ? opt->mode : select_mode(rmax);
   if (allow_coop && mode == 0) {
     FISDF_TRY(pchol_select_batch_launch(s, X2, scale, n, rmax, tol, piv, rank, work, handled,
-                                        coop_err));
+                                        coop_err, ran));
     if (*handled) return 0;
   }
   if (allow_coop && mode <= 1) {
     FISDF_TRY(pchol_select_coop_launch(s, X2, scale, n, rmax, tol, piv, rank, work, handled,
-                                       coop_err, progress));
+                                       coop_err, progress, opt, ran));
     if (*handled) {
       if (publishes) *publishes = progress != nullptr;
       return 0;
@@ -1778,6 +1825,7 @@ int pchol_select_real(hipStream_t s, const cplx* X2, double scale, int n, int rm
 #undef FISDF_PR
   FISDF_HIP(hipGetLastError());
   *handled = true;
+  if (ran) *ran = SelRan{SEL_RAN_PANEL, 1, rpt, pnb, 0};
   return 0;
 }
 

@@ -127,6 +127,12 @@ _SIGS = {
     "fisdf_k_wsrho_ex": ([_vp, _vp, _l, _ip, _dp, _vp, _l, _i, _dp, _ip], _i),
     "fisdf_bloch_dft_ex": ([_vp, _vp, _l, _ip, _vp, _ip], _i),
     "fisdf_bloch_band_ex": ([_vp, _vp, _l, _i, _vp, _i, _vp], _i),
+    # the selection piece by piece
+    "fisdf_select_plan": ([_i, _i, _i, _i, _i, _ip, _ip, C.POINTER(_l), _ip, C.POINTER(_l), _ip,
+                           _ip], _i),
+    "fisdf_select_pivots_ex": ([_vp, _vp, _i, _i, _i, _d, _i, _i, _i, _ip, _ip, _ip, _ip], _i),
+    "fisdf_select_gram_ex": ([_vp, _vp, _ip, _i, _i, _i, _i, _i, _i, _vp, _ip], _i),
+    "fisdf_select_gram_plan": ([_ip, _i, _i, _i, _i, _i, _i, _ip], _i),
     # composite entries
     "fisdf_build_opts_default": ([_vp], None),
     "fisdf_build": ([_vp, _vp, _i, _vp, _i, _ip, _ip, _dp, _vp, _ip], _i),

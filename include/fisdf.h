@@ -720,6 +720,50 @@ int fisdf_bloch_dft_ex(fisdf_ctx* ctx, const void* d_F, long ncol, const int kme
 int fisdf_bloch_band_ex(fisdf_ctx* ctx, const void* d_F, long ncol, int nT, const void* d_ph,
                         int nkb, void* d_chi);
 
+/* ---- the interpolation-point selection piece by piece, for tests of its dispatch.  Every pointer
+ * named d_ is device memory, every call with a context is synchronous and fails before it launches
+ * or copies anything when it cannot run, its outputs left as they were. ---- */
+/* what the selection does for an n x n Gram and rmax pivots (1 <= rmax <= n) on a device of ncu
+ * compute units, from the host functions its launchers use (no context, no device).  lds_cols and
+ * wgs: 0 = the production values, else what FISDF_SEL_LDS_COLS and FISDF_SEL_WGS would set.
+ * *h_mode: the kernel tried first when no switch is set (0 batch: from 800 pivots on, 1 coop); a
+ * kernel that does not take the sizes hands on to the next: batch, coop, panel, then the generic
+ * pivoted Cholesky.
+ * h_batch (4): taken or not, the rule that refused it (0 none, 1 n < 64, 2 n > 4096, 3 rmax > 4096,
+ *   4 more workgroups than ncu, 5 the owner's LDS above 150 KB, 6 the scratch beyond the n*n work
+ *   area), the grid (owners + leader), rows per owner; *h_batch_lds: dynamic LDS bytes.
+ * h_coop (7): taken or not, the rule that refused it (0 none, 1 n < 64, 2 no workgroup, 3 fewer
+ *   than 16 columns of the split form fit, 4 LDS above 150 KB, 5 more than 64 rows per workgroup,
+ *   6 the scratch beyond the work area), split form or not, G workgroups, RW rows per workgroup,
+ *   K columns of the owned rows in LDS, tpr threads per row; *h_coop_lds: dynamic LDS bytes.
+ *   Entries computed after the refusing rule are 0.
+ * h_panel (2): rows per thread and pivots per panel of the register-panel kernel (0, 0 beyond
+ *   n = 4096); *h_pchol_path: the generic path's (0 blocked, 1 per step).  Any output may be NULL */
+int fisdf_select_plan(int n, int rmax, int ncu, int lds_cols, int wgs, int* h_mode, int* h_batch,
+                      long* h_batch_lds, int* h_coop, long* h_coop_lds, int* h_panel,
+                      int* h_pchol_path);
+/* fisdf_select_pivots (nip_max <= ng0) with the switches as arguments.  mode: -1 as
+ * fisdf_select_pivots (the default rule and FISDF_SEL_MODE), 0 start at the batch kernel, 1 at the
+ * cooperative one, 2 the register panels only (FISDF_SEL_COOP then unread too); lds_cols, wgs as
+ * above, FISDF_SEL_LDS_COLS and FISDF_SEL_WGS unread.  h_perm: entries from *h_npiv on are left as they were.  h_info (6): what
+ * produced the pivots, which a refused kernel makes differ from the mode asked for: the kernel
+ * (0 batch, 1 coop, 2 coop in its split form, 3 register panels, 4 generic blocked, 5 generic per
+ * step), G, RW, K, tpr as in fisdf_select_plan (batch: the grid, 16, rmax, 0; panels: 1, rows per
+ * thread, pivots per panel, 0; generic: 0, 0, panel width, 0), and the passes (2: the first one
+ * reported a stalled step and the selection was redone without the co-resident kernels) */
+int fisdf_select_pivots_ex(fisdf_ctx* ctx, const void* d_x2, int nk, int ng0, int nip_max,
+                           double tol, int mode, int lds_cols, int wgs, int* h_perm, int* h_npiv,
+                           int* h_full_rank, int* h_info);
+/* fisdf_select_gram with an optional k-mesh (NULL, or axes whose product is nk) and the
+ * time-reversal fold as an argument: fold = 1 (needs the k-mesh, q0 = 0, q1 = nk) sums the
+ * representatives k <= -k, a paired one scaled by sqrt(2).  h_info (3, may be NULL): the k-points
+ * summed, the permute launches (64 k each under the fold) and the HERK split-K.  The _plan form
+ * gives h_info alone (no context, no device) */
+int fisdf_select_gram_ex(fisdf_ctx* ctx, const void* d_x0, const int* kmesh, int fold, int nk,
+                         int q0, int q1, int ng0, int nao, void* d_x2, int* h_info);
+int fisdf_select_gram_plan(const int* kmesh, int fold, int nk, int q0, int q1, int ng0, int nao,
+                           int* h_info);
+
 #ifdef __cplusplus
 }
 #endif

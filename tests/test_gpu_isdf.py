@@ -282,7 +282,10 @@ def test_selection_paths_agree(name, monkeypatch):
     LDS (forced here with FISDF_SEL_LDS_COLS; the default when the rows do not fit, as in C5) and
     the blocked right-looking one (FISDF_SEL_COOP=0) pick the same pivots as dpstrf on these
     cases."""
-    perms = {}
+    import torch
+    import select_cases as S
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    perms, ran = {}, {}
     for mode, env in (("batch", {"FISDF_SEL_COOP": "1", "FISDF_SEL_MODE": "batch"}),
                       ("coop", {"FISDF_SEL_COOP": "1", "FISDF_SEL_MODE": "coop"}),
                       ("split", {"FISDF_SEL_COOP": "1", "FISDF_SEL_MODE": "coop",
@@ -295,8 +298,15 @@ def test_selection_paths_agree(name, monkeypatch):
         df, o, dm = make_df(name, inject=False)
         df.build()
         perms[mode] = df.perm.copy()
+        # the kernel the mode names runs at this size (restated plan = the library's host
+        # functions, test_select_cases.py): a refused one would repeat another mode's kernel
+        n = df._ao_parent.shape[1]
+        rmax = max(1, min(int(df.cell.nao_nr() * df.c0), n))
+        ran[mode] = S.reached(n, rmax, ncu, {"batch": 0, "coop": 1, "split": 1, "blocked": 2}[mode],
+                              20 if mode == "split" else 0)[0]
     print(f"{name}: " + ", ".join(f"{m} == dpstrf: {np.array_equal(p, o['perm'])}"
                                   for m, p in perms.items()))
+    assert ran == {"batch": S.BATCH, "coop": S.COOP, "split": S.COOP_SPLIT, "blocked": S.PANEL}, ran
     for m, p in perms.items():
         assert np.array_equal(p, o["perm"]), m
 

@@ -162,6 +162,17 @@ def test_selection_batch_equals_coop(cfg, monkeypatch):
     else:
         cell, kmesh, c0, x0 = _cell_x0(cfg)
     nao = cell.nao_nr()
+    # the two modes are two kernels at this size (a refused one would hand on to the other and the
+    # comparison below would be of one kernel with itself): the restated plan, held equal to the
+    # library's host functions by test_select_cases.py
+    import torch
+    import select_cases as S
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    n, rmax = x0.shape[1], min(int(nao * c0), x0.shape[1])
+    ran = {"batch": S.reached(n, rmax, ncu, 0), "coop": S.reached(n, rmax, ncu, 1)}
+    print(f"{cfg}: n {n} rmax {rmax}: " + ", ".join(f"{m} -> {S.KERNEL_NAMES[r[0]]}"
+                                                     for m, r in ran.items()))
+    assert ran["batch"][0] == S.BATCH and ran["coop"][0] in (S.COOP, S.COOP_SPLIT)
     perms = {}
     for mode in ("coop", "batch"):
         monkeypatch.setenv("FISDF_SEL_MODE", mode)
