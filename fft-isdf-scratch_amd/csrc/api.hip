@@ -3470,6 +3470,131 @@ int fisdf_get_j_fft(fisdf_ctx* c, const void* fv, long f_kstride, const int kmes
                        cell_volume(a) / (double)ngl, (cplx*)vjv, (cplx*)((char*)base + oP), we);
 }
 
+// ---- exact FFT-grid K (PySCF fft_jk.get_k_kpts, the dm form; the kernels are in kfft.hip) -----
+int fisdf_kfft_plan(int nao, long ngrid, int nset, long work_bytes, int* h_mc, int* h_nchunk,
+                    int* h_run_len, int* h_nrun, int* h_pair_tw, int* h_exx_nn, long* h_row_bytes,
+                    long* h_bytes) {
+  t_cur_ctx = nullptr;
+  FISDF_CHECK(nao >= 1 && nao <= kKfftMaxNao && ngrid >= 1 && ngrid < (1L << 31) && nset >= 1 &&
+                  nset <= kKfftMaxSets && work_bytes >= 0,
+              "kfft_plan: bad sizes");
+  KfftPlan p;
+  kfft_plan(nao, ngrid, nset, work_bytes, &p);
+  if (h_mc) *h_mc = p.ok ? p.mc : 0;
+  if (h_nchunk) *h_nchunk = p.ok ? p.nchunk : 0;
+  if (h_run_len) *h_run_len = p.run_len;
+  if (h_nrun) *h_nrun = p.nrun;
+  if (h_pair_tw) *h_pair_tw = p.pair_tw;
+  if (h_exx_nn) *h_exx_nn = p.exx_nn;
+  if (h_row_bytes) *h_row_bytes = p.row_bytes;
+  if (h_bytes) *h_bytes = p.ok ? p.bytes : 0;
+  return 0;
+}
+
+int fisdf_pair_density(fisdf_ctx* c, const void* f1v, const void* f2v, int ngrid, int nao, int m0,
+                       int m1, void* outv) {
+  FISDF_TRY(device_guard(c));
+  StageTimer tm(c, FISDF_ST_K);
+  return pair_density(c->stream, (const cplx*)f1v, (const cplx*)f2v, ngrid, nao, m0, m1,
+                      (cplx*)outv);
+}
+
+int fisdf_exx_contract(fisdf_ctx* c, const void* zv, const void* uv, const void* f1v,
+                       const int mesh[3], const double* h_kd, int m0, int m1, int nao, int nset,
+                       double scale, void* vkv) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(mesh && mesh[0] >= 1 && mesh[1] >= 1 && mesh[2] >= 1, "exx_contract: bad mesh");
+  const long ngl = (long)mesh[0] * mesh[1] * mesh[2];
+  FISDF_CHECK(ngl < (1L << 31), "exx_contract: mesh too large");
+  FISDF_CHECK(nao >= 1 && nset >= 1, "exx_contract: sizes must be >= 1");
+  FISDF_CHECK(0 <= m0 && m0 < m1 && m1 <= nao, "exx_contract: bad row range");
+  StageTimer tm(c, FISDF_ST_K);
+  const long we = exx_contract_work_elems((int)ngl, nao, nset, m1 - m0);
+  void* base;
+  FISDF_TRY(arena_get(c, sizeof(cplx) * we, &base));
+  return exx_contract(c->stream, (const cplx*)zv, (const cplx*)uv, (const cplx*)f1v, mesh, h_kd,
+                      m0, m1, nao, nset, scale, 1, (cplx*)vkv, (long)nao * nao, (cplx*)base, we);
+}
+
+int fisdf_get_k_fft(fisdf_ctx* c, const void* fv, long f_kstride, const int kmesh[3],
+                    const int mesh[3], const double a[9], int nao, const void* dmsv, int nset,
+                    double omega, const void* fbandv, const double* h_kband, int nband,
+                    long work_bytes, void* vkv) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(fv && dmsv && vkv && kmesh, "get_k_fft: null pointer");
+  FISDF_CHECK(kmesh[0] >= 1 && kmesh[1] >= 1 && kmesh[2] >= 1, "get_k_fft: bad k-mesh");
+  FISDF_CHECK(nao >= 1 && nao <= kKfftMaxNao, "get_k_fft: nao must be in [1, 32768]");
+  FISDF_CHECK(nset <= kKfftMaxSets, "get_k_fft: more than 1024 sets");
+  FISDF_CHECK(nband >= 0 && work_bytes >= 0 && std::isfinite(omega), "get_k_fft: bad arguments");
+  FISDF_CHECK((fbandv != nullptr) == (nband > 0) && (fbandv == nullptr || h_kband != nullptr),
+              "get_k_fft: band AOs, band k-points and nband go together");
+  long ngl = 0;
+  FISDF_TRY(potential_check(mesh, a, nset, &ngl));
+  const long nkl = (long)kmesh[0] * kmesh[1] * kmesh[2];
+  FISDF_CHECK(nkl <= 65535, "get_k_fft: more than 65535 k-points");
+  FISDF_CHECK(f_kstride >= ngl * nao, "get_k_fft: f_kstride below ngrid * nao");
+  const int nk = (int)nkl, ngrid = (int)ngl;
+  KfftPlan p;
+  kfft_plan(nao, ngl, nset, work_bytes, &p);
+  FISDF_CHECK(p.ok, "get_k_fft: work_bytes below one row of m (nao transform rows of the grid)");
+  // fft3d makes its own checks of the mesh when the first transform is reached: until then only
+  // the arena is written, and d_vk is first written behind both transforms of the first block
+  const cplx* f = (const cplx*)fv;
+  const cplx* dms = (const cplx*)dmsv;
+  cplx* vk = (cplx*)vkv;
+  // K at the k-mesh from f itself, or at the band k-points from their AOs on the same grid
+  const cplx* fo = fbandv ? (const cplx*)fbandv : f;
+  const long fo_ks = fbandv ? ngl * nao : f_kstride;
+  const int no = fbandv ? nband : nk;
+  const long nn = (long)nao * nao;
+  CellGeom g;
+  lattice(a, g);
+  StageTimer tm(c, FISDF_ST_K);
+  void* base;
+  FISDF_TRY(arena_get(c, (size_t)p.bytes, &base));
+  cplx* rows = (cplx*)((char*)base + p.off_rows);
+  cplx* u = (cplx*)((char*)base + p.off_u);
+  double* w = (double*)((char*)base + p.off_w);
+  cplx* part = (cplx*)((char*)base + p.off_part);
+  const long part_elems = exx_contract_work_elems(ngrid, nao, nset, p.mc);
+  const double scale = cell_volume(a) / (double)ngl / (double)nk;
+  for (int k2 = 0; k2 < nk; ++k2) {
+    const cplx* f2 = f + (long)k2 * f_kstride;
+    double kq2[3];
+    kpoint(kmesh, g, k2, kq2);
+    // u_s = D[s][k2] f_k2^H, (nset, nao, ngrid)
+    FISDF_TRY(zgemm(c->stream, OP_N, OP_C, nao, ngrid, nao, ONE, dms + (long)k2 * nn, nao,
+                    (long)nk * nn, f2, nao, 0, ZERO, u, ngrid, (long)nao * ngrid, nset));
+    for (int k1 = 0; k1 < no; ++k1) {
+      const cplx* f1 = fo + (long)k1 * fo_ks;
+      double kq1[3], q[3], kd[3];
+      if (fbandv)
+        for (int d = 0; d < 3; ++d) kq1[d] = h_kband[3 * k1 + d];
+      else
+        kpoint(kmesh, g, k1, kq1);
+      for (int d = 0; d < 3; ++d) q[d] = kq2[d] - kq1[d];
+      for (int d = 0; d < 3; ++d) kd[d] = g.a[d][0] * q[0] + g.a[d][1] * q[1] + g.a[d][2] * q[2];
+      FISDF_TRY(coulg_weight(c->stream, mesh, g, q, 1.0 / (double)ngl, 0, w, omega));
+      for (int m0 = 0; m0 < nao; m0 += p.mc) {
+        const int m1 = std::min(nao, m0 + p.mc);
+        const int R = (m1 - m0) * nao;
+        FISDF_TRY(pair_density(c->stream, f1, f2, ngrid, nao, m0, m1, rows));
+        // vR conj(em)^-1 = ifft(coulG fft(pair em)) by the forward transform between conjugations;
+        // the second conjugation and conj(em) are the contraction's
+        FISDF_TRY(fft3d(c->stream, rows, ngl, nullptr, rows, ngl, R, mesh[0], mesh[1], mesh[2], kd,
+                        w, nullptr));
+        FISDF_TRY(conj_inplace(c->stream, rows, (long)R * ngl));
+        FISDF_TRY(fft3d(c->stream, rows, ngl, nullptr, rows, ngl, R, mesh[0], mesh[1], mesh[2],
+                        nullptr, nullptr, nullptr));
+        FISDF_TRY(exx_contract(c->stream, rows, u, f1, mesh, kd, m0, m1, nao, nset, scale,
+                               k2 > 0 ? 1 : 0, vk + (long)k1 * nn, (long)no * nn, part,
+                               part_elems));
+      }
+    }
+  }
+  return 0;
+}
+
 // ---- A8 -----------------------------------------------------------------------
 static int get_k_block(fisdf_ctx* c, const void* Xv, const double* Ws_rows, long ws_Rstride,
                        const void* dmsv, int nset, int nip, int nao, const int kmesh[3],

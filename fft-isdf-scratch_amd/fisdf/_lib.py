@@ -91,6 +91,12 @@ _SIGS = {
     "fisdf_coulomb_potential": ([_vp, _vp, _i, _ip, _dp, _d, _vp], _i),
     "fisdf_weighted_gram": ([_vp, _vp, _l, _i, _i, _i, _vp, _i, _i, _d, _vp], _i),
     "fisdf_get_j_fft": ([_vp, _vp, _l, _ip, _ip, _dp, _i, _vp, _i, _d, _vp, _i, _vp], _i),
+    # exact FFT-grid K
+    "fisdf_pair_density": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "fisdf_exx_contract": ([_vp, _vp, _vp, _vp, _ip, _dp, _i, _i, _i, _i, _d, _vp], _i),
+    "fisdf_get_k_fft": ([_vp, _vp, _l, _ip, _ip, _dp, _i, _vp, _i, _d, _vp, _dp, _i, _l, _vp], _i),
+    "fisdf_kfft_plan": ([_i, _l, _i, _l, _ip, _ip, _ip, _ip, _ip, _ip, C.POINTER(_l),
+                         C.POINTER(_l)], _i),
     "fisdf_get_eri": ([_vp, _vp, _i, _i, _ip, _vp, C.POINTER(_vp), _ip, _vp], _i),
     "fisdf_zgemm": ([_vp, _i, _i, _i, _i, _i, _dp, _vp, _l, _l, _vp, _l, _l, _dp, _vp, _l, _l,
                      _i, _i], _i),

@@ -166,9 +166,15 @@ class InterpolativeSeparableDensityFitting:
     # where J comes from: "isdf" = the fit's W_0 (the reference, fftisdf.py:133-171); "fft" = the
     # exact FFT-grid J (PySCF fft_jk.get_j_kpts: the density on the FFT grid, one forward and one
     # inverse FFT, one weighted AO Gram over the resident Bloch AOs) — no fitting error, and
-    # defined at any band k-point.  K is the ISDF K either way.
+    # defined at any band k-point.
     j_method = "isdf"
     J_METHODS = ("isdf", "fft")
+    # where K comes from: "isdf" = the fit's W_q (the reference, fftisdf.py:173-228); "fft" = the
+    # exact FFT-grid K (PySCF fft_jk.get_k_kpts, the dm form: per (k1, k2) the nao^2 pair densities
+    # transformed forth and back with coulG(k2 - k1) and contracted with D and the AOs) — no
+    # fitting error, defined at any band k-point, and nk^2 nao^2 pairs of FFTs per call.
+    k_method = "isdf"
+    K_METHODS = ("isdf", "fft")
 
     def __init__(self, cell, kpts, m0=None, c0=20.0, device=None, comm=None):
         self.cell = cell
@@ -382,16 +388,19 @@ class InterpolativeSeparableDensityFitting:
                omega=None, exxdiv=None):
         """fftisdf.py:390-408."""
         _check_j_method(self)
+        _check_k_method(self)
         if omega is not None and omega != 0:
             # range-separated kernel (PySCF get_coulG omega; the reference raises, :392-393):
             # W_q refitted once per omega with the attenuated weight, X and the AO inputs shared
             if exxdiv is not None:
                 raise NotImplementedError("exxdiv with a range-separated kernel")
-            if self.j_method == "fft" and not with_k:
-                # the grid J takes omega as an argument: no refit of W_q for it
-                return self._get_jk(dm, kpts, kpts_band, with_j, False, None, float(omega))
+            if ((self.j_method == "fft" or not with_j)
+                    and (self.k_method == "fft" or not with_k)):
+                # the grid J and K take omega as an argument: no refit of W_q for them
+                return self._get_jk(dm, kpts, kpts_band, with_j, with_k, None, float(omega))
             sub = self._omega_df(float(omega))
             sub.j_method = self.j_method     # the cached sub-object follows the parent's setting
+            sub.k_method = self.k_method
             return sub._get_jk(dm, kpts, kpts_band, with_j, with_k, None, float(omega))
         if exxdiv is not None and exxdiv != "ewald":
             # the reference raises for every exxdiv (:395-396); 'ewald' is added here as
@@ -402,7 +411,8 @@ class InterpolativeSeparableDensityFitting:
 
     def _get_jk(self, dm, kpts, kpts_band, with_j, with_k, exxdiv, j_omega):
         """get_jk on this object's fitted state; j_omega: the range-separation parameter of the
-        grid J (j_method = "fft"), which takes it as an argument rather than from the fit."""
+        grid J and K (j_method / k_method = "fft"), which take it as an argument rather than from
+        the fit."""
         kpts = self.kpts if kpts is None else np.asarray(kpts)
         if kpts.ndim == 1:                                            # _check_kpts single kpt
             raise NotImplementedError
@@ -412,7 +422,7 @@ class InterpolativeSeparableDensityFitting:
         # read-back each at the end: no host round trip between the two
         dms, ddms = _dms_to_dev(self, dm)
         if with_k:
-            vk = _get_k_dev(self, ddms, exxdiv, band)
+            vk = _get_k_dev(self, ddms, exxdiv, band, j_omega)
         if with_j:
             vj = _get_j_dev(self, ddms, band, j_omega)
         if vk is not None and vj is not None and vk.shape == vj.shape:
@@ -1021,8 +1031,79 @@ def _check_j_method(df_obj):
                          f"not {df_obj.j_method!r}")
 
 
-# device bytes of band AOs on the FFT grid evaluated at a time (J at off-mesh band k-points)
+def _check_k_method(df_obj):
+    if df_obj.k_method not in df_obj.K_METHODS:
+        raise ValueError(f"ISDF.k_method must be one of {list(df_obj.K_METHODS)}, "
+                         f"not {df_obj.k_method!r}")
+
+
+# device bytes of band AOs on the FFT grid evaluated at a time (J and K at off-mesh band k-points)
 BAND_BLOCK_BYTES = 1 << 28
+# byte budget of the exact K's transform rows (fisdf_get_k_fft work_bytes); 0 = the library's default
+KFFT_WORK_BYTES = 0
+
+
+def _band_grid_aos(df_obj, coords, kb):
+    """Bloch AOs at the band k-points kb on the FFT grid, device (len(kb), ngrid, nao)."""
+    cell = df_obj.cell
+    if df_obj.ao_on_gpu and hasattr(cell, "shells"):
+        from .ao import eval_ao_band_gpu
+        return eval_ao_band_gpu(df_obj.device, cell, coords, kb)
+    return df_obj.device.to_dev(bloch_ao(cell, coords, kb))   # a PySCF-protocol cell
+
+
+def _get_k_fft_dev(df_obj, ddms, exxdiv=None, band=None, omega=None):
+    """The exact FFT-grid K on the device (PySCF fft_jk.get_k_kpts), k_method = "fft", with the
+    Coulomb kernel coulG(k2 - k1, omega) (None: the omega this object was fitted with): on the
+    k-mesh one fisdf_get_k_fft over the resident Bloch AOs; at band k-points that are all on the
+    mesh rows of that; otherwise the band AOs on the FFT grid, a block of band points at a time,
+    as the output side of the same call.  exxdiv='ewald' adds madelung S D S on the mesh; off the
+    mesh PySCF adds it only to the band points that are mesh members, which is refused here."""
+    d = df_obj.device
+    if d.sharded(df_obj):
+        raise NotImplementedError('k_method = "fft" on a k-sharded object')
+    on_mesh = None
+    if band is not None:
+        try:
+            on_mesh, _ = df_obj._kidx(band)
+        except ValueError:
+            on_mesh = None
+        if on_mesh is None and exxdiv == "ewald":
+            raise NotImplementedError("exxdiv='ewald' at band k-points off the k-mesh")
+    cell = df_obj.cell
+    f = df_obj._grid_aos()
+    nk, ngrid, nao = f.shape
+    nset = ddms.shape[0]
+    if omega is None:
+        omega = getattr(df_obj, "_fit_omega", 0.0)
+    omega = float(omega)
+    km_c, km_p = _lib.iarr(df_obj._kmesh())
+    mesh_c, mesh_p = _lib.iarr(df_obj.mesh)
+    a_c, a_p = _lib.darr(np.asarray(cell.lattice_vectors(), float).ravel())
+    work = int(KFFT_WORK_BYTES)
+    if band is None or on_mesh is not None:
+        vk = d.empty(ddms.shape)
+        d.ctx.call("fisdf_get_k_fft", _lib.ptr(f), ngrid * nao, km_p, mesh_p, a_p, nao,
+                   _lib.ptr(ddms), nset, omega, None, None, 0, work, _lib.ptr(vk))
+        if exxdiv == "ewald":
+            _ewald_exxdiv_for_G0(df_obj, ddms, vk)
+        if on_mesh is not None:
+            vk = vk[:, d.torch.as_tensor(on_mesh.astype(np.int64), device=vk.device)]
+        return vk
+    nb = len(band)
+    vk = d.empty((nset, nb, nao, nao))
+    blk = max(1, int(BAND_BLOCK_BYTES // (16 * ngrid * nao)))
+    coords = df_obj.grids_coords()
+    for b0 in range(0, nb, blk):
+        b1 = min(nb, b0 + blk)
+        fb = _band_grid_aos(df_obj, coords, band[b0:b1])
+        kb_c, kb_p = _lib.darr(np.asarray(band[b0:b1], float).ravel())
+        out = d.empty((nset, b1 - b0, nao, nao))
+        d.ctx.call("fisdf_get_k_fft", _lib.ptr(f), ngrid * nao, km_p, mesh_p, a_p, nao,
+                   _lib.ptr(ddms), nset, omega, _lib.ptr(fb), kb_p, b1 - b0, work, _lib.ptr(out))
+        vk[:, b0:b1] = out
+        del fb
+    return vk
 
 
 def _get_j_fft_dev(df_obj, ddms, band=None, omega=None):
@@ -1072,11 +1153,7 @@ def _get_j_fft_dev(df_obj, ddms, band=None, omega=None):
     scale = abs(np.linalg.det(a)) / ngrid
     for b0 in range(0, nb, blk):
         b1 = min(nb, b0 + blk)
-        if df_obj.ao_on_gpu and hasattr(cell, "shells"):
-            from .ao import eval_ao_band_gpu
-            fb = eval_ao_band_gpu(d, cell, coords, band[b0:b1])
-        else:                                   # a PySCF-protocol cell: pbc_eval_gto at kb
-            fb = d.to_dev(bloch_ao(cell, coords, band[b0:b1]))
+        fb = _band_grid_aos(df_obj, coords, band[b0:b1])
         out = d.empty((nset, b1 - b0, nao, nao))
         d.ctx.call("fisdf_weighted_gram", _lib.ptr(fb), ngrid * nao, b1 - b0, ngrid, nao,
                    _lib.ptr(v), nset, 0, scale, _lib.ptr(out))
@@ -1125,16 +1202,21 @@ def _finish_j(vj, dm_kpts, kpts, kpts_band):
 def get_k_kpts(df_obj, dm_kpts, hermi=1, kpts=np.zeros((1, 3)), kpts_band=None, exxdiv=None):
     """fftisdf.py:173-228 (+ exxdiv='ewald' and kpts_band on the k-mesh, next-4)."""
     assert exxdiv in (None, "ewald")
+    _check_k_method(df_obj)
     dms, ddms = _dms_to_dev(df_obj, dm_kpts)
     band = _band_of(df_obj, np.asarray(kpts), kpts_band)
     return _format_band(_get_k_dev(df_obj, ddms, exxdiv, band).cpu().numpy(), dm_kpts, kpts_band,
                         kpts)
 
 
-def _get_k_dev(df_obj, ddms, exxdiv=None, band=None):
+def _get_k_dev(df_obj, ddms, exxdiv=None, band=None, omega=None):
     """vk on the device (fftisdf.py:204-225) for device dms (nset, nk, nao, nao).  band: K at
     band k-points ON the k-mesh (rows of the k-mesh K); a band k' off the mesh needs W_q at the
-    off-mesh q = k' - k, which the k-mesh fit does not produce (NotImplementedError)."""
+    off-mesh q = k' - k, which the k-mesh fit does not produce (NotImplementedError under
+    k_method = "isdf"; the exact K, k_method = "fft", has no such limit).  omega: see
+    _get_k_fft_dev (the ISDF K's kernel is in the fitted W_q)."""
+    if df_obj.k_method == "fft":
+        return _get_k_fft_dev(df_obj, ddms, exxdiv, band, omega)
     if band is not None:
         try:
             kidx, _ = df_obj._kidx(band)

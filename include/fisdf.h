@@ -519,6 +519,54 @@ int fisdf_get_j_fft(fisdf_ctx* ctx, const void* d_f, long f_kstride, const int k
                     const int mesh[3], const double a[9], int nao, const void* d_dms, int nset,
                     double omega, const void* d_fband, int nband, void* d_vj);
 
+/* ---- exact FFT-grid K (PySCF fft_jk.get_k_kpts, the dm form, exxdiv=None) ----------------------
+ * For output k-points k1 (the k-mesh, or band points with their AOs f1 on the FFT grid), every k2
+ * of the k-mesh, q = k2 - k1 and em[g] = exp(-i q.r_g):
+ *   pair[m,l,g] = conj(f1[g,m]) f_k2[g,l] em[g]
+ *   vR[m,l,g]   = ifft(coulG(q, omega) fft(pair[m,l,:]))[g] conj(em[g])
+ *   u_s[l,g]    = sum_t D[s][k2][l,t] conj(f_k2[g,t])
+ *   K[s][k1][m,n] += (vol/ngrid)/nk sum_g (sum_l vR[m,l,g] u_s[l,g]) f1[g,n]
+ * D is any complex matrix, K is not symmetrised.  No atomics: repeated calls agree bit for bit,
+ * and fisdf_get_k_fft's result does not depend on work_bytes.
+ *
+ * d_out[(m - m0) nao + l][g] = conj(f1[g,m]) f2[g,l] for m in [m0, m1): (m1 - m0) nao rows of
+ * ngrid; d_f1, d_f2 (ngrid, nao), the same pointer or not. */
+int fisdf_pair_density(fisdf_ctx* ctx, const void* d_f1, const void* d_f2, int ngrid, int nao,
+                       int m0, int m1, void* d_out);
+/* d_vk_k1[s][m][n] += scale sum_g t_s[m,g] f1[g,n] for m in [m0, m1), where
+ * t_s[m,g] = conj(em[g]) sum_l conj(Z[(m - m0) nao + l][g]) u[s][l][g] and
+ * conj(em[g]) = exp(+i frac(g).h_kd), frac the fftfreq fractions of the point's mesh indices
+ * (h_kd NULL: no phase).  d_z (m1 - m0) nao rows of ngrid, d_u (nset, nao, ngrid), d_f1 (ngrid,
+ * nao), d_vk_k1 (nset, nao, nao): rows outside [m0, m1) are left as they are.  The grid is split
+ * into runs (fisdf_kfft_plan) whose partial blocks are summed in run order. */
+int fisdf_exx_contract(fisdf_ctx* ctx, const void* d_z, const void* d_u, const void* d_f1,
+                       const int mesh[3], const double* h_kd /*3 or NULL*/, int m0, int m1,
+                       int nao, int nset, double scale, void* d_vk_k1);
+/* The whole exact K: d_vk (nset, nk, nao, nao) for the k-mesh (d_fband NULL, nband 0), or with
+ * d_fband (nband, ngrid, nao) the AOs at the nband band k-points h_kband (nband x 3, Cartesian,
+ * 1/bohr, as fisdf_eval_ao_band takes them) d_vk (nset, nband, nao, nao) at those.  d_f (nk,
+ * ngrid, nao) with k stride f_kstride, d_dms (nset, nk, nao, nao).  omega is an argument (the
+ * context's setting is neither read nor changed).  work_bytes: the byte budget of the transform
+ * rows, 0 = the default (512 MiB), never more than nao rows m are taken; below one row m (nao
+ * rows of ngrid complex) is an error.  The argument checks come before the first launch; the FFT's
+ * own checks of the mesh run when the first transform is reached, when only the arena has been
+ * written.  Either way a refused call leaves d_vk untouched.  nao up to 32768, nset up to 1024.
+ * Workspace: the context's arena (fisdf_kfft_plan's bytes).  Asynchronous on the context's
+ * stream. */
+int fisdf_get_k_fft(fisdf_ctx* ctx, const void* d_f, long f_kstride, const int kmesh[3],
+                    const int mesh[3], const double a[9], int nao, const void* d_dms, int nset,
+                    double omega, const void* d_fband, const double* h_kband, int nband,
+                    long work_bytes, void* d_vk);
+/* what fisdf_get_k_fft does for given sizes, from the host functions its launchers use (no
+ * context, no device): rows m per chunk and chunks (both 0: the budget is below one row m), the
+ * contraction's grid runs (points per run, runs), the pair kernel's AO tile width (8 or 32), the
+ * contraction's n-tiles per thread (1, 2, 4; nao > 128 runs the last once per group of 128
+ * columns, reading Z once per group), the bytes of one row m and the arena bytes of the call.
+ * nao > 32768 or nset > 1024 is an error.  Any output may be NULL */
+int fisdf_kfft_plan(int nao, long ngrid, int nset, long work_bytes, int* h_mc, int* h_nchunk,
+                    int* h_run_len, int* h_nrun, int* h_pair_tw, int* h_exx_nn, long* h_row_bytes,
+                    long* h_bytes);
+
 /* ---- ISDF 4-index integrals (get_eri / ao2mo surface) --------------------------
  * eri[i*n2+j][k*n4+l] = sum_IJ W_q[I,J] conj(A1[I,i]) A2[I,j] conj(A3[J,k]) A4[J,l] with
  * A_s = X_{kidx[s]} C_s, q = k2 - k1 (fftdf-with-k-lstsq.py:221-232).  d_Wq: the (nip,nip)
