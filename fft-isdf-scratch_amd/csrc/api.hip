@@ -3595,6 +3595,167 @@ int fisdf_get_k_fft(fisdf_ctx* c, const void* fv, long f_kstride, const int kmes
   return 0;
 }
 
+// ---- exact FFT-grid K, the occupied-orbital form (the kernels are in kfft_lr.hip) -------------
+int fisdf_kfft_lr_plan(int nao, long ngrid, int nset, int imax, long work_bytes, int* h_mc,
+                       int* h_nchunk, int* h_run_len, int* h_nrun, int* h_pair_tw, int* h_exx_sc,
+                       int* h_exx_nn, long* h_row_bytes, long* h_bytes) {
+  t_cur_ctx = nullptr;
+  FISDF_CHECK(nao >= 1 && nao <= kKfftMaxNao && ngrid >= 1 && ngrid < (1L << 31) && nset >= 1 &&
+                  nset <= kKfftMaxSets && imax >= 1 && imax <= kKfftMaxNao && work_bytes >= 0,
+              "kfft_lr_plan: bad sizes");
+  KfftLrPlan p;
+  kfft_lr_plan(nao, ngrid, nset, imax, work_bytes, &p);
+  if (h_mc) *h_mc = p.ok ? p.mc : 0;
+  if (h_nchunk) *h_nchunk = p.ok ? p.nchunk : 0;
+  if (h_run_len) *h_run_len = p.run_len;
+  if (h_nrun) *h_nrun = p.nrun;
+  if (h_pair_tw) *h_pair_tw = p.pair_tw;
+  if (h_exx_sc) *h_exx_sc = p.exx_sc;
+  if (h_exx_nn) *h_exx_nn = p.exx_nn;
+  if (h_row_bytes) *h_row_bytes = p.row_bytes;
+  if (h_bytes) *h_bytes = p.ok ? p.bytes : 0;
+  return 0;
+}
+
+int fisdf_pair_density_lr(fisdf_ctx* c, const void* f1v, int nao, const void* psiv, int ni,
+                          long ld_psi, int ngrid, int m0, int m1, void* outv) {
+  FISDF_TRY(device_guard(c));
+  StageTimer tm(c, FISDF_ST_K);
+  return pair_density_lr(c->stream, (const cplx*)f1v, nao, (const cplx*)psiv, ni, ld_psi, ngrid,
+                         m0, m1, (cplx*)outv);
+}
+
+int fisdf_exx_contract_lr(fisdf_ctx* c, const void* zv, const void* uv, const void* f1v,
+                          const int mesh[3], const double* h_kd, int m0, int m1, int nao, int ni,
+                          const int* h_seg, int nset, double scale, void* vkv) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(mesh && mesh[0] >= 1 && mesh[1] >= 1 && mesh[2] >= 1, "exx_contract_lr: bad mesh");
+  const long ngl = (long)mesh[0] * mesh[1] * mesh[2];
+  FISDF_CHECK(ngl < (1L << 31), "exx_contract_lr: mesh too large");
+  FISDF_CHECK(nao >= 1 && nset >= 1 && ni >= 1, "exx_contract_lr: sizes must be >= 1");
+  FISDF_CHECK(0 <= m0 && m0 < m1 && m1 <= nao, "exx_contract_lr: bad row range");
+  StageTimer tm(c, FISDF_ST_K);
+  const long we = exx_contract_lr_work_elems((int)ngl, nao, nset, m1 - m0);
+  void* base;
+  FISDF_TRY(arena_get(c, sizeof(cplx) * we, &base));
+  return exx_contract_lr(c->stream, (const cplx*)zv, (const cplx*)uv, (const cplx*)f1v, mesh, h_kd,
+                         m0, m1, nao, ni, h_seg, nset, scale, 1, (cplx*)vkv, (long)nao * nao,
+                         (cplx*)base, we);
+}
+
+int fisdf_get_k_fft_lr(fisdf_ctx* c, const void* fv, long f_kstride, const int kmesh[3],
+                       const int mesh[3], const double a[9], int nao, const void* Av,
+                       const void* Bv, const int* h_rank, int rmax, int nset, double omega,
+                       const void* fbandv, const double* h_kband, int nband, long work_bytes,
+                       void* vkv) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(fv && Av && Bv && h_rank && vkv && kmesh, "get_k_fft_lr: null pointer");
+  FISDF_CHECK(kmesh[0] >= 1 && kmesh[1] >= 1 && kmesh[2] >= 1, "get_k_fft_lr: bad k-mesh");
+  FISDF_CHECK(nao >= 1 && nao <= kKfftMaxNao, "get_k_fft_lr: nao must be in [1, 32768]");
+  FISDF_CHECK(nset <= kKfftMaxSets, "get_k_fft_lr: more than 1024 sets");
+  FISDF_CHECK(rmax >= 1 && rmax <= kKfftMaxNao, "get_k_fft_lr: rmax must be in [1, 32768]");
+  FISDF_CHECK(nband >= 0 && work_bytes >= 0 && std::isfinite(omega), "get_k_fft_lr: bad arguments");
+  FISDF_CHECK((fbandv != nullptr) == (nband > 0) && (fbandv == nullptr || h_kband != nullptr),
+              "get_k_fft_lr: band AOs, band k-points and nband go together");
+  long ngl = 0;
+  FISDF_TRY(potential_check(mesh, a, nset, &ngl));
+  const long nkl = (long)kmesh[0] * kmesh[1] * kmesh[2];
+  FISDF_CHECK(nkl <= 65535, "get_k_fft_lr: more than 65535 k-points");
+  FISDF_CHECK(f_kstride >= ngl * nao, "get_k_fft_lr: f_kstride below ngrid * nao");
+  const int nk = (int)nkl, ngrid = (int)ngl;
+  long imax = 0;
+  for (int k = 0; k < nk; ++k) {
+    long ik = 0;
+    for (int s = 0; s < nset; ++s) {
+      const int r = h_rank[(long)s * nk + k];
+      FISDF_CHECK(r >= 0 && r <= rmax, "get_k_fft_lr: rank outside [0, rmax]");
+      ik += r;
+    }
+    imax = std::max(imax, ik);
+  }
+  FISDF_CHECK(imax <= kKfftMaxNao, "get_k_fft_lr: more than 32768 orbitals at one k-point");
+  const cplx* f = (const cplx*)fv;
+  const cplx* A = (const cplx*)Av;
+  const cplx* B = (const cplx*)Bv;
+  cplx* vk = (cplx*)vkv;
+  // K at the k-mesh from f itself, or at the band k-points from their AOs on the same grid
+  const cplx* fo = fbandv ? (const cplx*)fbandv : f;
+  const long fo_ks = fbandv ? ngl * nao : f_kstride;
+  const int no = fbandv ? nband : nk;
+  const long nn = (long)nao * nao, nr = (long)nao * rmax;
+  StageTimer tm(c, FISDF_ST_K);
+  if (imax == 0) {  // no k2 has an orbital: K = 0 (nothing is transformed, the mesh is not read)
+    FISDF_HIP(hipMemsetAsync(vk, 0, sizeof(cplx) * (size_t)nset * no * nn, c->stream));
+    return 0;
+  }
+  KfftLrPlan p;
+  kfft_lr_plan(nao, ngl, nset, (int)imax, work_bytes, &p);
+  FISDF_CHECK(p.ok, "get_k_fft_lr: work_bytes below one row of m (the transform rows of the "
+                    "orbitals of the fullest k-point)");
+  // fft3d makes its own checks of the mesh when the first transform is reached: until then only
+  // the arena is written, and d_vk is first written behind both transforms of the first block
+  CellGeom g;
+  lattice(a, g);
+  void* base;
+  FISDF_TRY(arena_get(c, (size_t)p.bytes, &base));
+  cplx* rows = (cplx*)((char*)base + p.off_rows);
+  cplx* psi = (cplx*)((char*)base + p.off_psi);
+  cplx* u = (cplx*)((char*)base + p.off_u);
+  double* w = (double*)((char*)base + p.off_w);
+  cplx* part = (cplx*)((char*)base + p.off_part);
+  const long part_elems = exx_contract_lr_work_elems(ngrid, nao, nset, p.mc);
+  const double scale = cell_volume(a) / (double)ngl / (double)nk;
+  std::vector<int> seg(nset + 1);
+  bool first = true;  // the first k2 that has work overwrites d_vk, the later ones add
+  for (int k2 = 0; k2 < nk; ++k2) {
+    seg[0] = 0;
+    for (int s = 0; s < nset; ++s) seg[s + 1] = seg[s] + h_rank[(long)s * nk + k2];
+    const int ni = seg[nset];
+    if (ni == 0) continue;
+    const cplx* f2 = f + (long)k2 * f_kstride;
+    double kq2[3];
+    kpoint(kmesh, g, k2, kq2);
+    // the orbitals of every set on the grid: psi[:, segment s] = f_k2 A[s][k2][:, :r_s], (ngrid,
+    // ni), and u[segment s] = (B[s][k2][:, :r_s])^H f_k2^H = conj(psiB)^T, (ni, ngrid)
+    for (int s = 0; s < nset; ++s) {
+      const int r = seg[s + 1] - seg[s];
+      if (r == 0) continue;
+      const long sk = ((long)s * nk + k2) * nr;
+      FISDF_TRY(zgemm(c->stream, OP_N, OP_N, ngrid, r, nao, ONE, f2, nao, 0, A + sk, rmax, 0, ZERO,
+                      psi + seg[s], ni, 0, 1));
+      FISDF_TRY(zgemm(c->stream, OP_C, OP_C, r, ngrid, nao, ONE, B + sk, rmax, 0, f2, nao, 0, ZERO,
+                      u + (long)seg[s] * ngrid, ngrid, 0, 1));
+    }
+    for (int k1 = 0; k1 < no; ++k1) {
+      const cplx* f1 = fo + (long)k1 * fo_ks;
+      double kq1[3], q[3], kd[3];
+      if (fbandv)
+        for (int d = 0; d < 3; ++d) kq1[d] = h_kband[3 * k1 + d];
+      else
+        kpoint(kmesh, g, k1, kq1);
+      for (int d = 0; d < 3; ++d) q[d] = kq2[d] - kq1[d];
+      for (int d = 0; d < 3; ++d) kd[d] = g.a[d][0] * q[0] + g.a[d][1] * q[1] + g.a[d][2] * q[2];
+      FISDF_TRY(coulg_weight(c->stream, mesh, g, q, 1.0 / (double)ngl, 0, w, omega));
+      for (int m0 = 0; m0 < nao; m0 += p.mc) {
+        const int m1 = std::min(nao, m0 + p.mc);
+        const int R = (m1 - m0) * ni;
+        FISDF_TRY(pair_density_lr(c->stream, f1, nao, psi, ni, ni, ngrid, m0, m1, rows));
+        // the transform pair of the dm form (fisdf_get_k_fft) over (m1 - m0) ni rows
+        FISDF_TRY(fft3d(c->stream, rows, ngl, nullptr, rows, ngl, R, mesh[0], mesh[1], mesh[2], kd,
+                        w, nullptr));
+        FISDF_TRY(conj_inplace(c->stream, rows, (long)R * ngl));
+        FISDF_TRY(fft3d(c->stream, rows, ngl, nullptr, rows, ngl, R, mesh[0], mesh[1], mesh[2],
+                        nullptr, nullptr, nullptr));
+        FISDF_TRY(exx_contract_lr(c->stream, rows, u, f1, mesh, kd, m0, m1, nao, ni, seg.data(),
+                                  nset, scale, first ? 0 : 1, vk + (long)k1 * nn, (long)no * nn,
+                                  part, part_elems));
+      }
+    }
+    first = false;
+  }
+  return 0;
+}
+
 // ---- A8 -----------------------------------------------------------------------
 static int get_k_block(fisdf_ctx* c, const void* Xv, const double* Ws_rows, long ws_Rstride,
                        const void* dmsv, int nset, int nip, int nao, const int kmesh[3],

@@ -243,4 +243,38 @@ struct KfftPlan {
 };
 void kfft_plan(int nao, long ngrid, int nset, long work_bytes, KfftPlan* p);
 
+// ---- exact FFT-grid K, the occupied-orbital (low-rank) form (kfft_lr.hip) ----
+// D[s][k2] = A B^H with r_s columns: the orbitals of all sets stacked, ni = sum_s r_s rows per row
+// m where the dm form has nao, set s owning the segment [seg[s], seg[s + 1]).
+constexpr int kLrRows = 32;     // rows (set, m) per workgroup of the segmented contraction
+constexpr int kLrSetChunk = 2;  // sets per launch: 32 rows m per workgroup for one set, 16 for two
+// P[(m - m0) ni + i][g] = conj(f1[g,m]) psi[g,i] for m in [m0, m1): f1 (ngrid, nao), psi (ngrid,
+// ni) at leading dimension ld.  pair_density_lr_variant: the orbital tile width (8, 32)
+int pair_density_lr(hipStream_t s, const cplx* f1, int nao, const cplx* psi, int ni, long ld,
+                    int ngrid, int m0, int m1, cplx* P);
+int pair_density_lr_variant(int ni);
+// vk[s][m][n] (+)= scale sum_g t_s[m,g] f1[g,n] for m in [m0, m1), with
+// t_s[m,g] = exp(+i frac(g).kd) sum_{i in segment s} conj(Z[(m - m0) ni + i][g]) u[i][g]; Z
+// (m1 - m0) ni rows of ngrid, u (ni, ngrid), seg nset + 1 host offsets from 0 to ni (an empty
+// segment gives zeros).  Runs, reduction, accumulate and vk_set as exx_contract; at most
+// kLrSetChunk sets per launch, each launch reading only its sets' rows of Z.  work:
+// exx_contract_lr_work_elems complex elements.  The n-tiles per thread are exx_contract_variant's
+int exx_contract_lr(hipStream_t s, const cplx* Z, const cplx* u, const cplx* f1, const int mesh[3],
+                    const double* kd, int m0, int m1, int nao, int ni, const int* seg, int nset,
+                    double scale, int accumulate, cplx* vk, long vk_set, cplx* work,
+                    long work_elems);
+long exx_contract_lr_work_elems(int ngrid, int nao, int nset, int mc);
+// What fisdf_get_k_fft_lr does for given sizes, imax the largest ni of a k2, and a byte budget for
+// the transform rows (0: kKfftWorkBytes): as KfftPlan with row_bytes = imax transform rows; the
+// arena also holds the orbitals on the grid (psi and u, imax rows each).
+struct KfftLrPlan {
+  int ok = 0;
+  int mc = 0, nchunk = 0;
+  int run_len = 0, nrun = 0;
+  int pair_tw = 0, exx_sc = 0, exx_nn = 0;
+  long row_bytes = 0;
+  long off_rows = 0, off_psi = 0, off_u = 0, off_w = 0, off_part = 0, bytes = 0;
+};
+void kfft_lr_plan(int nao, long ngrid, int nset, int imax, long work_bytes, KfftLrPlan* p);
+
 }  // namespace fisdf

@@ -97,6 +97,13 @@ _SIGS = {
     "fisdf_get_k_fft": ([_vp, _vp, _l, _ip, _ip, _dp, _i, _vp, _i, _d, _vp, _dp, _i, _l, _vp], _i),
     "fisdf_kfft_plan": ([_i, _l, _i, _l, _ip, _ip, _ip, _ip, _ip, _ip, C.POINTER(_l),
                          C.POINTER(_l)], _i),
+    # exact FFT-grid K, the occupied-orbital (low-rank) form
+    "fisdf_pair_density_lr": ([_vp, _vp, _i, _vp, _i, _l, _i, _i, _i, _vp], _i),
+    "fisdf_exx_contract_lr": ([_vp, _vp, _vp, _vp, _ip, _dp, _i, _i, _i, _i, _ip, _i, _d, _vp], _i),
+    "fisdf_get_k_fft_lr": ([_vp, _vp, _l, _ip, _ip, _dp, _i, _vp, _vp, _ip, _i, _i, _d, _vp, _dp,
+                            _i, _l, _vp], _i),
+    "fisdf_kfft_lr_plan": ([_i, _l, _i, _i, _l, _ip, _ip, _ip, _ip, _ip, _ip, _ip, C.POINTER(_l),
+                            C.POINTER(_l)], _i),
     "fisdf_get_eri": ([_vp, _vp, _i, _i, _ip, _vp, C.POINTER(_vp), _ip, _vp], _i),
     "fisdf_zgemm": ([_vp, _i, _i, _i, _i, _i, _dp, _vp, _l, _l, _vp, _l, _l, _dp, _vp, _l, _l,
                      _i, _i], _i),

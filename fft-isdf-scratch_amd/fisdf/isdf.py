@@ -175,6 +175,17 @@ class InterpolativeSeparableDensityFitting:
     # fitting error, defined at any band k-point, and nk^2 nao^2 pairs of FFTs per call.
     k_method = "isdf"
     K_METHODS = ("isdf", "fft")
+    # which form of the exact K (read only when k_method = "fft"): "dm" = all nao^2 pair densities
+    # per (k1, k2); "lowrank" = the occupied-orbital form of fft_jk.get_k_kpts, D = A B^H with r
+    # columns and nao r pair densities — the factors from the dm's mo_coeff / mo_occ tags
+    # (tag_array; trusted, as PySCF trusts them) or else from a host SVD of every D[s][k] that
+    # keeps sigma > k_rank_tol sigma_max(set s) (None: nao eps, numpy.linalg.matrix_rank's rule);
+    # "auto" = "lowrank" when it has fewer transform rows, sum_k r_k < K_AUTO_ROW_RATIO nk nao.
+    # k_form_used: what the last exact K took.
+    k_form = "dm"
+    K_FORMS = ("dm", "lowrank", "auto")
+    k_rank_tol = None
+    k_form_used = None
 
     def __init__(self, cell, kpts, m0=None, c0=20.0, device=None, comm=None):
         self.cell = cell
@@ -401,7 +412,10 @@ class InterpolativeSeparableDensityFitting:
             sub = self._omega_df(float(omega))
             sub.j_method = self.j_method     # the cached sub-object follows the parent's setting
             sub.k_method = self.k_method
-            return sub._get_jk(dm, kpts, kpts_band, with_j, with_k, None, float(omega))
+            sub.k_form, sub.k_rank_tol = self.k_form, self.k_rank_tol
+            out = sub._get_jk(dm, kpts, kpts_band, with_j, with_k, None, float(omega))
+            self.k_form_used = sub.k_form_used
+            return out
         if exxdiv is not None and exxdiv != "ewald":
             # the reference raises for every exxdiv (:395-396); 'ewald' is added here as
             # PySCF's FFTDF does it: K + madelung * S_k D_k S_k
@@ -422,7 +436,7 @@ class InterpolativeSeparableDensityFitting:
         # read-back each at the end: no host round trip between the two
         dms, ddms = _dms_to_dev(self, dm)
         if with_k:
-            vk = _get_k_dev(self, ddms, exxdiv, band, j_omega)
+            vk = _get_k_dev(self, ddms, exxdiv, band, j_omega, dm)
         if with_j:
             vj = _get_j_dev(self, ddms, band, j_omega)
         if vk is not None and vj is not None and vk.shape == vj.shape:
@@ -1035,12 +1049,85 @@ def _check_k_method(df_obj):
     if df_obj.k_method not in df_obj.K_METHODS:
         raise ValueError(f"ISDF.k_method must be one of {list(df_obj.K_METHODS)}, "
                          f"not {df_obj.k_method!r}")
+    if df_obj.k_method == "fft" and df_obj.k_form not in df_obj.K_FORMS:
+        raise ValueError(f"ISDF.k_form must be one of {list(df_obj.K_FORMS)}, "
+                         f"not {df_obj.k_form!r}")
+
+
+class TaggedArray(np.ndarray):
+    """An ndarray that carries attributes (PySCF's tagged-array convention: a density matrix with
+    the ``mo_coeff`` and ``mo_occ`` it was made from).  ``np.asarray`` of it is the plain array."""
+
+    def __array_finalize__(self, obj):
+        if isinstance(obj, TaggedArray):
+            self.__dict__.update(obj.__dict__)
+
+
+def tag_array(a, **tags):
+    """``a`` as a TaggedArray with ``tags`` as attributes, e.g. ``tag_array(dm, mo_coeff=C,
+    mo_occ=n)`` (PySCF ``lib.tag_array``) — what k_form = "lowrank" reads its orbitals from."""
+    t = np.asarray(a).view(TaggedArray)
+    if isinstance(a, TaggedArray):
+        t.__dict__.update(a.__dict__)
+    t.__dict__.update(tags)
+    return t
+
+
+def lowrank_factors(dm, tol=None):
+    """(A, B, ranks) with D[s][k] = A[s, k, :, :r] B[s, k, :, :r]^H, r = ranks[s, k]: A and B
+    (nset, nk, nao, rmax) complex, zero beyond r, rmax = max(1, ranks.max()); ranks (nset, nk) int32.
+    dm is (nk, nao, nao) or (nset, nk, nao, nao).
+
+    A dm tagged with ``mo_coeff`` ((nk, nao, nmo), with a leading set axis where dm has one; a
+    sequence per k-point will do) and ``mo_occ`` ((nk, nmo) likewise) gives the orbitals with
+    occupation != 0: A = C occ, B = C.  The tags are trusted, dm itself is not read.  Otherwise an
+    SVD of each D[s][k] — Hermitian or not, one code path: D = U S V^H, A = U S, B = V — keeping
+    sigma > tol sigma_max(set s); tol None: nao eps, the rule of numpy.linalg.matrix_rank."""
+    plain = np.asarray(dm)
+    nao = plain.shape[-1]
+    has_set = plain.ndim == 4
+    shape = plain.shape if has_set else (1,) + plain.shape
+    nset, nk = shape[:2]
+    cols = [[None] * nk for _ in range(nset)]
+    C, occ = getattr(dm, "mo_coeff", None), getattr(dm, "mo_occ", None)
+    if C is not None and occ is not None:
+        if not has_set:
+            C, occ = [C], [occ]
+        for s in range(nset):
+            for k in range(nk):
+                c, n = np.asarray(C[s][k], complex), np.asarray(occ[s][k], float)
+                keep = n != 0
+                cols[s][k] = (c[:, keep] * n[keep], c[:, keep])
+    else:
+        D = plain.reshape(shape).astype(complex)
+        if tol is None:
+            tol = nao * np.finfo(float).eps
+        for s in range(nset):
+            usv = [np.linalg.svd(D[s, k]) for k in range(nk)]
+            smax = max(sv[0] for _, sv, _ in usv)
+            for k, (U, sv, Vh) in enumerate(usv):
+                r = int(np.count_nonzero(sv > tol * smax))
+                cols[s][k] = (U[:, :r] * sv[:r], Vh[:r].conj().T)
+    ranks = np.array([[cols[s][k][0].shape[1] for k in range(nk)] for s in range(nset)], np.int32)
+    rmax = max(1, int(ranks.max()))
+    A = np.zeros((nset, nk, nao, rmax), complex)
+    B = np.zeros((nset, nk, nao, rmax), complex)
+    for s in range(nset):
+        for k in range(nk):
+            A[s, k, :, :ranks[s, k]], B[s, k, :, :ranks[s, k]] = cols[s][k]
+    return A, B, ranks
 
 
 # device bytes of band AOs on the FFT grid evaluated at a time (J and K at off-mesh band k-points)
 BAND_BLOCK_BYTES = 1 << 28
 # byte budget of the exact K's transform rows (fisdf_get_k_fft work_bytes); 0 = the library's default
 KFFT_WORK_BYTES = 0
+# k_form = "auto" takes the low-rank form when sum_k r_k < K_AUTO_ROW_RATIO nk nao.  Both forms make
+# the same passes over a transform row, so the row counts decide, but not at 1: at equal row counts
+# (C3 shape, 2x2x2 k-mesh, rank 26 = nao) the low-rank call measured 85.49 ms against the dm form's
+# 81.76 ms (its contraction is slower at full rank, and it forms the orbitals), a ratio of 0.956,
+# rounded down (DESIGN 3.11)
+K_AUTO_ROW_RATIO = 0.95
 
 
 def _band_grid_aos(df_obj, coords, kb):
@@ -1052,13 +1139,32 @@ def _band_grid_aos(df_obj, coords, kb):
     return df_obj.device.to_dev(bloch_ao(cell, coords, kb))   # a PySCF-protocol cell
 
 
-def _get_k_fft_dev(df_obj, ddms, exxdiv=None, band=None, omega=None):
+def _k_factors(df_obj, dm, ddms):
+    """The factors of k_form "lowrank" / "auto" — (A, B, ranks) of lowrank_factors — or None for
+    the dm form.  dm: what the caller gave (its tags are read), None: the device dms alone."""
+    if df_obj.k_form == "dm":
+        return None
+    nk = ddms.shape[1]
+    tagged = getattr(dm, "mo_coeff", None) is not None and getattr(dm, "mo_occ", None) is not None
+    if tagged and (np.ndim(dm) == 4 or (np.ndim(dm) == 3 and np.shape(dm)[0] == nk)):
+        src = dm
+    else:
+        src = ddms.cpu().numpy() if dm is None else _format_dms(dm, nk)
+    A, B, ranks = lowrank_factors(src, df_obj.k_rank_tol)
+    if df_obj.k_form == "auto" and not ranks.sum() < K_AUTO_ROW_RATIO * nk * ddms.shape[2]:
+        return None
+    return A, B, ranks
+
+
+def _get_k_fft_dev(df_obj, ddms, exxdiv=None, band=None, omega=None, dm=None):
     """The exact FFT-grid K on the device (PySCF fft_jk.get_k_kpts), k_method = "fft", with the
     Coulomb kernel coulG(k2 - k1, omega) (None: the omega this object was fitted with): on the
     k-mesh one fisdf_get_k_fft over the resident Bloch AOs; at band k-points that are all on the
     mesh rows of that; otherwise the band AOs on the FFT grid, a block of band points at a time,
     as the output side of the same call.  exxdiv='ewald' adds madelung S D S on the mesh; off the
-    mesh PySCF adds it only to the band points that are mesh members, which is refused here."""
+    mesh PySCF adds it only to the band points that are mesh members, which is refused here.
+    k_form "lowrank" / "auto": the same calls to fisdf_get_k_fft_lr with the factors of _k_factors
+    (dm: the caller's array, for its tags) in place of the dms; everything else is unchanged."""
     d = df_obj.device
     if d.sharded(df_obj):
         raise NotImplementedError('k_method = "fft" on a k-sharded object')
@@ -1081,10 +1187,24 @@ def _get_k_fft_dev(df_obj, ddms, exxdiv=None, band=None, omega=None):
     mesh_c, mesh_p = _lib.iarr(df_obj.mesh)
     a_c, a_p = _lib.darr(np.asarray(cell.lattice_vectors(), float).ravel())
     work = int(KFFT_WORK_BYTES)
+    fac = _k_factors(df_obj, dm, ddms)
+    df_obj.k_form_used = "dm" if fac is None else "lowrank"
+    if fac is None:
+        def get_k(fb, kb_p, nb, out):
+            d.ctx.call("fisdf_get_k_fft", _lib.ptr(f), ngrid * nao, km_p, mesh_p, a_p, nao,
+                       _lib.ptr(ddms), nset, omega, fb, kb_p, nb, work, _lib.ptr(out))
+    else:
+        dA, dB = d.to_dev(fac[0]), d.to_dev(fac[1])
+        rk_c, rk_p = _lib.iarr(fac[2].ravel())
+        rmax = fac[0].shape[-1]
+
+        def get_k(fb, kb_p, nb, out):
+            d.ctx.call("fisdf_get_k_fft_lr", _lib.ptr(f), ngrid * nao, km_p, mesh_p, a_p, nao,
+                       _lib.ptr(dA), _lib.ptr(dB), rk_p, rmax, nset, omega, fb, kb_p, nb, work,
+                       _lib.ptr(out))
     if band is None or on_mesh is not None:
         vk = d.empty(ddms.shape)
-        d.ctx.call("fisdf_get_k_fft", _lib.ptr(f), ngrid * nao, km_p, mesh_p, a_p, nao,
-                   _lib.ptr(ddms), nset, omega, None, None, 0, work, _lib.ptr(vk))
+        get_k(None, None, 0, vk)
         if exxdiv == "ewald":
             _ewald_exxdiv_for_G0(df_obj, ddms, vk)
         if on_mesh is not None:
@@ -1099,8 +1219,7 @@ def _get_k_fft_dev(df_obj, ddms, exxdiv=None, band=None, omega=None):
         fb = _band_grid_aos(df_obj, coords, band[b0:b1])
         kb_c, kb_p = _lib.darr(np.asarray(band[b0:b1], float).ravel())
         out = d.empty((nset, b1 - b0, nao, nao))
-        d.ctx.call("fisdf_get_k_fft", _lib.ptr(f), ngrid * nao, km_p, mesh_p, a_p, nao,
-                   _lib.ptr(ddms), nset, omega, _lib.ptr(fb), kb_p, b1 - b0, work, _lib.ptr(out))
+        get_k(_lib.ptr(fb), kb_p, b1 - b0, out)
         vk[:, b0:b1] = out
         del fb
     return vk
@@ -1205,18 +1324,19 @@ def get_k_kpts(df_obj, dm_kpts, hermi=1, kpts=np.zeros((1, 3)), kpts_band=None, 
     _check_k_method(df_obj)
     dms, ddms = _dms_to_dev(df_obj, dm_kpts)
     band = _band_of(df_obj, np.asarray(kpts), kpts_band)
-    return _format_band(_get_k_dev(df_obj, ddms, exxdiv, band).cpu().numpy(), dm_kpts, kpts_band,
-                        kpts)
+    return _format_band(_get_k_dev(df_obj, ddms, exxdiv, band, None, dm_kpts).cpu().numpy(),
+                        dm_kpts, kpts_band, kpts)
 
 
-def _get_k_dev(df_obj, ddms, exxdiv=None, band=None, omega=None):
+def _get_k_dev(df_obj, ddms, exxdiv=None, band=None, omega=None, dm=None):
     """vk on the device (fftisdf.py:204-225) for device dms (nset, nk, nao, nao).  band: K at
     band k-points ON the k-mesh (rows of the k-mesh K); a band k' off the mesh needs W_q at the
     off-mesh q = k' - k, which the k-mesh fit does not produce (NotImplementedError under
     k_method = "isdf"; the exact K, k_method = "fft", has no such limit).  omega: see
-    _get_k_fft_dev (the ISDF K's kernel is in the fitted W_q)."""
+    _get_k_fft_dev (the ISDF K's kernel is in the fitted W_q).  dm: the caller's array, whose
+    tags the exact K's k_form = "lowrank" reads."""
     if df_obj.k_method == "fft":
-        return _get_k_fft_dev(df_obj, ddms, exxdiv, band, omega)
+        return _get_k_fft_dev(df_obj, ddms, exxdiv, band, omega, dm)
     if band is not None:
         try:
             kidx, _ = df_obj._kidx(band)

@@ -567,6 +567,53 @@ int fisdf_kfft_plan(int nao, long ngrid, int nset, long work_bytes, int* h_mc, i
                     int* h_run_len, int* h_nrun, int* h_pair_tw, int* h_exx_nn, long* h_row_bytes,
                     long* h_bytes);
 
+/* ---- exact FFT-grid K, the occupied-orbital (low-rank) form ---------------------------------------
+ * D[s][k2] = A B^H with A, B (nao, r), r = r[s][k2] (any dm has such factors: D = U S V^H gives
+ * A = U S, B = V; occupied orbitals C with occupations n give A = C n, B = C).  With the orbitals on
+ * the grid psiA_i(g) = sum_l f_k2[g,l] A[l,i], psiB_i(g) = sum_t f_k2[g,t] B[t,i], and em, q, coulG
+ * and the output points k1 those of the dm form above:
+ *   pair[m,i,g] = conj(f1[g,m]) psiA_i(g) em[g]
+ *   vR[m,i,g]   = ifft(coulG(q, omega) fft(pair[m,i,:]))[g] conj(em[g])
+ *   K[s][k1][m,n] += (vol/ngrid)/nk sum_g (sum_{i<r} vR[m,i,g] conj(psiB_i(g))) f1[g,n]
+ * The transform rows of one k2 are the orbitals of all sets stacked, ni = sum_s r[s][k2] per row m
+ * where the dm form has nao, set s owning the segment [seg[s], seg[s+1]).  No atomics: repeated
+ * calls agree bit for bit, and fisdf_get_k_fft_lr's result does not depend on work_bytes.
+ *
+ * d_out[(m - m0) ni + i][g] = conj(f1[g,m]) psi[g,i] for m in [m0, m1): (m1 - m0) ni rows of
+ * ngrid; d_f1 (ngrid, nao), d_psi (ngrid, ni) with leading dimension ld_psi >= ni. */
+int fisdf_pair_density_lr(fisdf_ctx* ctx, const void* d_f1, int nao, const void* d_psi, int ni,
+                          long ld_psi, int ngrid, int m0, int m1, void* d_out);
+/* d_vk_k1[s][m][n] += scale sum_g t_s[m,g] f1[g,n] for m in [m0, m1), where
+ * t_s[m,g] = conj(em[g]) sum_{i in [h_seg[s], h_seg[s+1])} conj(Z[(m - m0) ni + i][g]) u[i][g],
+ * conj(em) as in fisdf_exx_contract.  d_z (m1 - m0) ni rows of ngrid, d_u (ni, ngrid) = conj(psiB)
+ * transposed, d_f1 (ngrid, nao), d_vk_k1 (nset, nao, nao); h_seg nset + 1 offsets, h_seg[0] = 0,
+ * not decreasing, h_seg[nset] = ni.  Every element of d_z is read once and meets one set; an
+ * empty segment adds exact zeros.  Runs and their order as fisdf_exx_contract. */
+int fisdf_exx_contract_lr(fisdf_ctx* ctx, const void* d_z, const void* d_u, const void* d_f1,
+                          const int mesh[3], const double* h_kd /*3 or NULL*/, int m0, int m1,
+                          int nao, int ni, const int* h_seg /*nset+1 offsets*/, int nset,
+                          double scale, void* d_vk_k1);
+/* The whole exact K from the factors: d_A, d_B (nset, nk, nao, rmax), of which only the first
+ * h_rank[s nk + k] columns are ever read; every other argument, the output, the checks and the
+ * workspace as fisdf_get_k_fft, with the transform rows of one row m now those of the fullest
+ * k-point, imax = max_k sum_s h_rank[s nk + k] (work_bytes below imax rows of ngrid complex is an
+ * error).  A rank below 0 or above rmax, or rmax < 1, is an error.  A k2 without orbitals launches
+ * nothing: the first k2 that has some overwrites d_vk, and when no k2 has any d_vk is set to zero
+ * (nothing is transformed then, so the mesh is not checked by the FFT). */
+int fisdf_get_k_fft_lr(fisdf_ctx* ctx, const void* d_f, long f_kstride, const int kmesh[3],
+                       const int mesh[3], const double a[9], int nao, const void* d_A,
+                       const void* d_B, const int* h_rank /*nset*nk*/, int rmax, int nset,
+                       double omega, const void* d_fband, const double* h_kband, int nband,
+                       long work_bytes, void* d_vk);
+/* what fisdf_get_k_fft_lr does for given sizes and imax >= 1 (host only): rows m per chunk =
+ * min(nao, budget / (imax ngrid 16)) and chunks (both 0: the budget is below one row m), the
+ * contraction's grid runs, the pair kernel's orbital tile width (8 or 32), the sets per launch of
+ * the contraction (1 or 2: 32 or 16 rows m per workgroup) and its n-tiles per thread (1, 2, 4), the
+ * bytes of one row m and the arena bytes of the call.  Any output may be NULL */
+int fisdf_kfft_lr_plan(int nao, long ngrid, int nset, int imax, long work_bytes, int* h_mc,
+                       int* h_nchunk, int* h_run_len, int* h_nrun, int* h_pair_tw, int* h_exx_sc,
+                       int* h_exx_nn, long* h_row_bytes, long* h_bytes);
+
 /* ---- ISDF 4-index integrals (get_eri / ao2mo surface) --------------------------
  * eri[i*n2+j][k*n4+l] = sum_IJ W_q[I,J] conj(A1[I,i]) A2[I,j] conj(A3[J,k]) A4[J,l] with
  * A_s = X_{kidx[s]} C_s, q = k2 - k1 (fftdf-with-k-lstsq.py:221-232).  d_Wq: the (nip,nip)
