@@ -124,6 +124,11 @@ struct fisdf_ctx {
   int pipe_mode = -1;   // fisdf_set_fit_pipe; -1: environment FISDF_FIT_PIPE (default on)
   int pipe_depth = 0;   // ring slots; 0: lanes + 2
   int last_fit_lanes = 0, last_fit_pipe = 0;  // what the last fisdf_fit_coulomb_qs ran with
+  // fisdf_fit_report: what the last fisdf_fit_coulomb_qs did for each q of its list
+  struct FitRec {
+    int v[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  };
+  std::vector<FitRec> fit_report;
   std::vector<hipEvent_t> ev_ready;  // fisdf_mark_y_ready: y of local q j landed (sharded fit)
   std::vector<char> ready_marked;
   // fisdf_set_y_slices: y of local q j read in place from its all-to-all piece (grid slices)
@@ -748,6 +753,7 @@ int check_qlist(const int* qs, int nq, int nk, const char* who) {
 // partials cost 2 ks n^2 x 16 B of extra traffic).
 int pick_ksplit_herk(int n, int K, int ncu) {
   const long nt = (n + 63) / 64, tiles = nt * (nt + 1) / 2;
+  if (tiles == 0) return 1;  // n = 0: a rank-0 q beside others in one fit call
   const long slots = 3L * ncu;
   int best = 1;
   double best_eff = 0;
@@ -770,6 +776,24 @@ int pick_ksplit(int M, int N, int K) {
   int ks = 1;
   while (tiles * ks < 1024 && K / (ks * 2) >= 512) ks *= 2;
   return ks;
+}
+
+// whether a fit call of nq q runs each q's W_PP in its lane (when every q is full rank and none
+// is a minimum-norm slot; the batched tail otherwise).  FISDF_LANE_WPP: 0 never, 1 always
+constexpr int kLaneWppMinQ = 12;
+bool lane_wpp_wanted(int nq) {
+  static const int lane_wpp_env = [] {
+    const char* e = getenv("FISDF_LANE_WPP");
+    return e ? atoi(e) : -1;
+  }();
+  return lane_wpp_env < 0 ? nq >= kLaneWppMinQ : lane_wpp_env != 0;
+}
+
+// split-K of the W_PP GEMMs: from nip alone.  FISDF_WPP_KSPLIT (read per call; 1 = off)
+int wpp_ksplit(int nip) {
+  const char* e = getenv("FISDF_WPP_KSPLIT");
+  const int v = e ? atoi(e) : 4;
+  return (nip >= 256 && v > 1) ? std::min(v, 16) : 1;
 }
 
 }  // namespace
@@ -2468,6 +2492,31 @@ int fisdf_fit_info(fisdf_ctx* c, int* h_lanes, int* h_pipe_depth) {
   return 0;
 }
 
+int fisdf_fit_report(fisdf_ctx* c, int j, int info[12]) {
+  FISDF_TRY(ctx_guard(c));
+  FISDF_CHECK(c != nullptr && info != nullptr, "fit_report: null argument");
+  FISDF_CHECK(j >= 0 && j < (int)c->fit_report.size(), "fit_report: no such q in the last fit");
+  for (int i = 0; i < 12; ++i) info[i] = c->fit_report[j].v[i];
+  return 0;
+}
+
+int fisdf_fit_plan(const int kmesh[3], const int mesh[3], int q, int nq, int nip, int info[8]) {
+  FISDF_CHECK(kmesh && mesh && info, "fit_plan: null argument");
+  FISDF_CHECK(kmesh[0] >= 1 && kmesh[1] >= 1 && kmesh[2] >= 1 && mesh[0] >= 1 && mesh[1] >= 1 &&
+                  mesh[2] >= 1 && q >= 0 && q < kmesh[0] * kmesh[1] * kmesh[2],
+              "fit_plan: bad sizes");
+  const bool self = self_conjugate(kmesh, q);
+  int m[3] = {0, 0, 0};
+  if (self) self_conjugate_m(kmesh, q, m);
+  info[0] = self ? 1 : 0;
+  for (int d = 0; d < 3; ++d) info[1 + d] = m[d];
+  info[4] = self ? half_prefix_planes(mesh[0], m[0]) : mesh[0];
+  info[5] = info[4] * mesh[1] * mesh[2];
+  info[6] = lane_wpp_wanted(nq) ? 1 : 0;
+  info[7] = wpp_ksplit(nip);
+  return 0;
+}
+
 int fisdf_reserve_workspace(fisdf_ctx* c, size_t bytes) {
   FISDF_TRY(device_guard(c));
   void* base;
@@ -2734,13 +2783,7 @@ int fisdf_fit_coulomb_qs(fisdf_ctx* c, const int* h_qs, int nq, const void* yTv,
   // 1: W_q unchanged bit for bit).  C3 on one GPU (36 q): 79.89 vs 80.21 ms/step; a k-shard's 4-5
   // q: +0.6 ms per rank (the last q of each lane then waits for its own small GEMMs), so below
   // kLaneWppMinQ q the batched tail stays.  FISDF_LANE_WPP: 0 never, 1 always
-  constexpr int kLaneWppMinQ = 12;
-  static const int lane_wpp_env = [] {
-    const char* e = getenv("FISDF_LANE_WPP");
-    return e ? atoi(e) : -1;
-  }();
-  bool lane_wpp = (lane_wpp_env < 0 ? nq >= kLaneWppMinQ : lane_wpp_env != 0) && rmax == nip &&
-                  ncod == 0;
+  bool lane_wpp = lane_wpp_wanted(nq) && rmax == nip && ncod == 0;
   for (int lq = 0; lq < nq && lane_wpp; ++lq) lane_wpp = c->f_rank[s0 + lq] == nip;
   // split-K of each q's HERK from its own rank (not the call's largest), so a q's arithmetic
   // does not depend on which other q share the call (1-GPU vs sharded builds agree bitwise)
@@ -2775,11 +2818,28 @@ int fisdf_fit_coulomb_qs(fisdf_ctx* c, const int* h_qs, int nq, const void* yTv,
   // of 64 x 64 at C3 leave most CUs idle for ~180 us per GEMM, in every lane, for every q.  The
   // split depends on nip only, the same in the lanes and in the batched tail (W_q bitwise equal
   // between the 1-GPU and the k-sharded builds).  FISDF_WPP_KSPLIT (read per call; 1 = off)
-  const int wks = [&] {
-    const char* e = getenv("FISDF_WPP_KSPLIT");
-    const int v = e ? atoi(e) : 4;
-    return (nip >= 256 && v > 1) ? std::min(v, 16) : 1;
-  }();
+  const int wks = wpp_ksplit(nip);
+  // the record fisdf_fit_report reads (what is decided here; the FFT form and the asymmetric
+  // count are filled in where they are found)
+  {
+    bool all_full = rmax == nip;
+    for (int lq = 0; lq < nq && all_full; ++lq) all_full = c->f_rank[s0 + lq] == nip;
+    c->fit_report.assign(nq, fisdf_ctx::FitRec{});
+    for (int lq = 0; lq < nq; ++lq) {
+      int* v = c->fit_report[lq].v;
+      const int sl = s0 + lq, r = c->f_rank[sl];
+      v[0] = r;
+      v[1] = c->f_real[sl] ? 1 : 0;
+      v[2] = half_of(sl) ? 1 : 0;
+      v[4] = (int)ncols_of(lq);
+      v[6] = r == 0 ? -1 : cod_of(sl) ? 1 : r == nip ? 0 : 2;
+      v[7] = cod_of(sl) ? 1 : 0;
+      v[8] = lq % NL;
+      v[9] = lane_wpp ? 1 : all_full ? 0 : 2;
+      v[10] = (lane_wpp || all_full) ? wks : 1;
+      v[11] = piece_of(lq) ? (unpack ? 2 : 1) : 0;
+    }
+  }
   const size_t oWk = wks > 1 ? cv.take(sizeof(cplx) * (size_t)NL * wks * rr) : 0;
   size_t oG = cv.take(sizeof(cplx) * nq * rr);
   size_t oT = cv.take(sizeof(cplx) * nq * rr);
@@ -2867,6 +2927,7 @@ int fisdf_fit_coulomb_qs(fisdf_ctx* c, const int* h_qs, int nq, const void* yTv,
       }
     }
     const int* hm = herm ? herm_m : nullptr;
+    c->fit_report[lq].v[3] = fft3d_route(mesh[0], mesh[1], mesh[2], hm) == FFT_REG_HERM ? 1 : 0;
     // y of this q stored real by the composite build's y kernel (fisdf_build_y_qs)
     const bool y_real = yT != nullptr && lq < (int)c->y_real_slot.size() && c->y_real_slot[lq];
     StageTimer tm(c, FISDF_ST_FFT, st);
@@ -2979,19 +3040,26 @@ int fisdf_fit_coulomb_qs(fisdf_ctx* c, const int* h_qs, int nq, const void* yTv,
         if (half_of(sl)) {
           // half grid: one member of each asymmetric pair, Im W = Im(U_A diag(f) U_A^H)
           FISDF_TRY(get_asym_half(c, st, mesh, kmesh, a, q, wscale, &as));
-          if (as->n > 0) {
+          c->fit_report[lq].v[5] = as->n;
+          // scratch holds r x ngrid: the plain and the scaled copy of at most ngrid / 2 listed
+          // columns at a time (one pass unless more than half the grid is listed, which takes a
+          // mesh whose planes are all self-paired, n0 <= 2)
+          const int cap = (int)std::max(1L, ngrid / 2);
+          for (int o = 0; o < as->n; o += cap) {
+            const int na = std::min(cap, as->n - o);
             cplx* plain = scratch;
-            cplx* scaled = scratch + (long)r * as->n;
-            FISDF_TRY(gather_cols_scaled(st, Uq, ngrid, r, as->idx, nullptr, as->n, plain));
-            FISDF_TRY(gather_cols_scaled(st, Uq, ngrid, r, as->idx, as->f, as->n, scaled));
-            FISDF_TRY(zgemm(st, OP_N, OP_C, r, r, as->n, ONE, scaled, as->n, 0, plain, as->n, 0, ZERO,
-                            Tc, rmax, 0, 1, std::min(ks_of(r, ncol), std::max(1, as->n / 256)), kw));
+            cplx* scaled = scratch + (long)r * na;
+            FISDF_TRY(gather_cols_scaled(st, Uq, ngrid, r, as->idx + o, nullptr, na, plain));
+            FISDF_TRY(gather_cols_scaled(st, Uq, ngrid, r, as->idx + o, as->f + o, na, scaled));
+            FISDF_TRY(zgemm(st, OP_N, OP_C, r, r, na, ONE, scaled, na, 0, plain, na, 0, ZERO, Tc,
+                            rmax, 0, 1, std::min(ks_of(r, ncol), std::max(1, na / 256)), kw));
             FISDF_TRY(add_imag(st, G + lq * rr, rmax, Tc, rmax, r));
           }
         } else {
           const double* wt = nullptr;
           FISDF_TRY(weight_q(st, lq, &wt));
           FISDF_TRY(get_asym(c, st, mesh, kmesh, a, q, wt, &as));
+          c->fit_report[lq].v[5] = as->n;
           if (as->n > 0) {
             FISDF_TRY(gather_cols(st, Uq, ngrid, r, as->idx, as->n, scratch));
             FISDF_TRY(herk(st, r, as->n, 1.0, scratch, as->n, Tc, rmax,

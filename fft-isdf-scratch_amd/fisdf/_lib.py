@@ -74,6 +74,8 @@ _SIGS = {
     "fisdf_set_time_reversal": ([_vp, _i], _i),
     "fisdf_set_fit_pipe": ([_vp, _i, _i], _i),
     "fisdf_fit_info": ([_vp, _ip, _ip], _i),
+    "fisdf_fit_report": ([_vp, _i, _ip], _i),
+    "fisdf_fit_plan": ([_ip, _ip, _i, _i, _i, _ip], _i),
     "fisdf_mark_y_ready": ([_vp, _i], _i),
     "fisdf_set_y_slices": ([_vp, _i, _vp, _i, C.POINTER(_l), C.POINTER(_l)], _i),
     "fisdf_reserve_workspace": ([_vp, C.c_size_t], _i),

@@ -406,6 +406,22 @@ int fisdf_set_factor_priority(fisdf_ctx* ctx, int high);
 int fisdf_set_fit_pipe(fisdf_ctx* ctx, int mode, int depth);
 /* What the last fisdf_fit_coulomb_qs ran with: MFMA lanes and ring depth (0 = not pipelined). */
 int fisdf_fit_info(fisdf_ctx* ctx, int* h_lanes, int* h_pipe_depth);
+/* What the last fisdf_fit_coulomb_qs that passed its argument checks did for the j-th q of its
+ * list (read-only, for tests of its dispatch).  info: [0] rank; [1] real factor; [2] half-grid
+ * weights; [3] the FFT took its Hermitian-paired form (register meshes); [4] grid columns fitted;
+ * [5] weight-asymmetric G listed (0 for a q without a real factor); [6] the solve that formed U:
+ * 0 one lower-triangular GEMM with L^-1, 1 the minimum-norm operator, 2 the blocked substitution
+ * (basic solution of a short rank), -1 none (rank 0); [7] minimum-norm slot; [8] lane; [9] W_PP:
+ * 0 the batched tail's two triangular GEMMs, 1 in the lane, 2 the batched tail's blocked
+ * substitution; [10] split-K of the W_PP GEMMs (1 where they did not run); [11] y read from:
+ * 0 d_yT, 1 plane slices in place, 2 plane slices unpacked first. */
+int fisdf_fit_report(fisdf_ctx* ctx, int j, int info[12]);
+/* The fit's host-side rules for q of a k-mesh on a mesh, in a call of nq q with nip points (no
+ * context, no device).  info: [0] q is its own time-reversal partner; [1..3] m = 2 k_q in
+ * reciprocal-lattice units (0 otherwise); [4] the half grid's prefix planes (mesh[0] for a q
+ * that is not self-conjugate); [5] its columns; [6] nq is large enough for W_PP in the lanes
+ * (FISDF_LANE_WPP overrides); [7] split-K of the W_PP GEMMs (FISDF_WPP_KSPLIT, read per call). */
+int fisdf_fit_plan(const int kmesh[3], const int mesh[3], int q, int nq, int nip, int info[8]);
 /* Sharded build: record, on the context's stream, that y of the j-th q of the NEXT
  * fisdf_fit_coulomb_qs call has landed in d_yT (after its all-to-all piece is unpacked).  When
  * every q of that call is marked, the call runs its lanes on side streams and starts each q's
