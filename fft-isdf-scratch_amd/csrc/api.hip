@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <set>
@@ -3538,7 +3539,22 @@ int fisdf_get_j_fft(fisdf_ctx* c, const void* fv, long f_kstride, const int kmes
                        cell_volume(a) / (double)ngl, (cplx*)vjv, (cplx*)((char*)base + oP), we);
 }
 
-// ---- exact FFT-grid K (PySCF fft_jk.get_k_kpts, the dm form; the kernels are in kfft.hip) -----
+// ---- exact FFT-grid K (PySCF fft_jk.get_k_kpts) in the dm form and the occupied-orbital form; the
+// kernels and the plan are in kfft.hip ------------------------------------------------------------
+static void kfft_plan_report(const KfftPlan& p, int* h_mc, int* h_nchunk, int* h_run_len,
+                             int* h_nrun, int* h_pair_tw, int* h_exx_sc, int* h_exx_nn,
+                             long* h_row_bytes, long* h_bytes) {
+  if (h_mc) *h_mc = p.ok ? p.mc : 0;
+  if (h_nchunk) *h_nchunk = p.ok ? p.nchunk : 0;
+  if (h_run_len) *h_run_len = p.run_len;
+  if (h_nrun) *h_nrun = p.nrun;
+  if (h_pair_tw) *h_pair_tw = p.pair_tw;
+  if (h_exx_sc) *h_exx_sc = p.exx_sc;
+  if (h_exx_nn) *h_exx_nn = p.exx_nn;
+  if (h_row_bytes) *h_row_bytes = p.row_bytes;
+  if (h_bytes) *h_bytes = p.ok ? p.bytes : 0;
+}
+
 int fisdf_kfft_plan(int nao, long ngrid, int nset, long work_bytes, int* h_mc, int* h_nchunk,
                     int* h_run_len, int* h_nrun, int* h_pair_tw, int* h_exx_nn, long* h_row_bytes,
                     long* h_bytes) {
@@ -3547,15 +3563,23 @@ int fisdf_kfft_plan(int nao, long ngrid, int nset, long work_bytes, int* h_mc, i
                   nset <= kKfftMaxSets && work_bytes >= 0,
               "kfft_plan: bad sizes");
   KfftPlan p;
-  kfft_plan(nao, ngrid, nset, work_bytes, &p);
-  if (h_mc) *h_mc = p.ok ? p.mc : 0;
-  if (h_nchunk) *h_nchunk = p.ok ? p.nchunk : 0;
-  if (h_run_len) *h_run_len = p.run_len;
-  if (h_nrun) *h_nrun = p.nrun;
-  if (h_pair_tw) *h_pair_tw = p.pair_tw;
-  if (h_exx_nn) *h_exx_nn = p.exx_nn;
-  if (h_row_bytes) *h_row_bytes = p.row_bytes;
-  if (h_bytes) *h_bytes = p.ok ? p.bytes : 0;
+  kfft_plan(nao, ngrid, nset, nao, false, work_bytes, &p);
+  kfft_plan_report(p, h_mc, h_nchunk, h_run_len, h_nrun, h_pair_tw, nullptr, h_exx_nn, h_row_bytes,
+                   h_bytes);
+  return 0;
+}
+
+int fisdf_kfft_lr_plan(int nao, long ngrid, int nset, int imax, long work_bytes, int* h_mc,
+                       int* h_nchunk, int* h_run_len, int* h_nrun, int* h_pair_tw, int* h_exx_sc,
+                       int* h_exx_nn, long* h_row_bytes, long* h_bytes) {
+  t_cur_ctx = nullptr;
+  FISDF_CHECK(nao >= 1 && nao <= kKfftMaxNao && ngrid >= 1 && ngrid < (1L << 31) && nset >= 1 &&
+                  nset <= kKfftMaxSets && imax >= 1 && imax <= kKfftMaxNao && work_bytes >= 0,
+              "kfft_lr_plan: bad sizes");
+  KfftPlan p;
+  kfft_plan(nao, ngrid, nset, imax, true, work_bytes, &p);
+  kfft_plan_report(p, h_mc, h_nchunk, h_run_len, h_nrun, h_pair_tw, h_exx_sc, h_exx_nn, h_row_bytes,
+                   h_bytes);
   return 0;
 }
 
@@ -3577,112 +3601,11 @@ int fisdf_exx_contract(fisdf_ctx* c, const void* zv, const void* uv, const void*
   FISDF_CHECK(nao >= 1 && nset >= 1, "exx_contract: sizes must be >= 1");
   FISDF_CHECK(0 <= m0 && m0 < m1 && m1 <= nao, "exx_contract: bad row range");
   StageTimer tm(c, FISDF_ST_K);
-  const long we = exx_contract_work_elems((int)ngl, nao, nset, m1 - m0);
+  const long we = exx_contract_work_elems((int)ngl, nao, nset, m1 - m0, kJfftSetChunk);
   void* base;
   FISDF_TRY(arena_get(c, sizeof(cplx) * we, &base));
   return exx_contract(c->stream, (const cplx*)zv, (const cplx*)uv, (const cplx*)f1v, mesh, h_kd,
                       m0, m1, nao, nset, scale, 1, (cplx*)vkv, (long)nao * nao, (cplx*)base, we);
-}
-
-int fisdf_get_k_fft(fisdf_ctx* c, const void* fv, long f_kstride, const int kmesh[3],
-                    const int mesh[3], const double a[9], int nao, const void* dmsv, int nset,
-                    double omega, const void* fbandv, const double* h_kband, int nband,
-                    long work_bytes, void* vkv) {
-  FISDF_TRY(device_guard(c));
-  FISDF_CHECK(fv && dmsv && vkv && kmesh, "get_k_fft: null pointer");
-  FISDF_CHECK(kmesh[0] >= 1 && kmesh[1] >= 1 && kmesh[2] >= 1, "get_k_fft: bad k-mesh");
-  FISDF_CHECK(nao >= 1 && nao <= kKfftMaxNao, "get_k_fft: nao must be in [1, 32768]");
-  FISDF_CHECK(nset <= kKfftMaxSets, "get_k_fft: more than 1024 sets");
-  FISDF_CHECK(nband >= 0 && work_bytes >= 0 && std::isfinite(omega), "get_k_fft: bad arguments");
-  FISDF_CHECK((fbandv != nullptr) == (nband > 0) && (fbandv == nullptr || h_kband != nullptr),
-              "get_k_fft: band AOs, band k-points and nband go together");
-  long ngl = 0;
-  FISDF_TRY(potential_check(mesh, a, nset, &ngl));
-  const long nkl = (long)kmesh[0] * kmesh[1] * kmesh[2];
-  FISDF_CHECK(nkl <= 65535, "get_k_fft: more than 65535 k-points");
-  FISDF_CHECK(f_kstride >= ngl * nao, "get_k_fft: f_kstride below ngrid * nao");
-  const int nk = (int)nkl, ngrid = (int)ngl;
-  KfftPlan p;
-  kfft_plan(nao, ngl, nset, work_bytes, &p);
-  FISDF_CHECK(p.ok, "get_k_fft: work_bytes below one row of m (nao transform rows of the grid)");
-  // fft3d makes its own checks of the mesh when the first transform is reached: until then only
-  // the arena is written, and d_vk is first written behind both transforms of the first block
-  const cplx* f = (const cplx*)fv;
-  const cplx* dms = (const cplx*)dmsv;
-  cplx* vk = (cplx*)vkv;
-  // K at the k-mesh from f itself, or at the band k-points from their AOs on the same grid
-  const cplx* fo = fbandv ? (const cplx*)fbandv : f;
-  const long fo_ks = fbandv ? ngl * nao : f_kstride;
-  const int no = fbandv ? nband : nk;
-  const long nn = (long)nao * nao;
-  CellGeom g;
-  lattice(a, g);
-  StageTimer tm(c, FISDF_ST_K);
-  void* base;
-  FISDF_TRY(arena_get(c, (size_t)p.bytes, &base));
-  cplx* rows = (cplx*)((char*)base + p.off_rows);
-  cplx* u = (cplx*)((char*)base + p.off_u);
-  double* w = (double*)((char*)base + p.off_w);
-  cplx* part = (cplx*)((char*)base + p.off_part);
-  const long part_elems = exx_contract_work_elems(ngrid, nao, nset, p.mc);
-  const double scale = cell_volume(a) / (double)ngl / (double)nk;
-  for (int k2 = 0; k2 < nk; ++k2) {
-    const cplx* f2 = f + (long)k2 * f_kstride;
-    double kq2[3];
-    kpoint(kmesh, g, k2, kq2);
-    // u_s = D[s][k2] f_k2^H, (nset, nao, ngrid)
-    FISDF_TRY(zgemm(c->stream, OP_N, OP_C, nao, ngrid, nao, ONE, dms + (long)k2 * nn, nao,
-                    (long)nk * nn, f2, nao, 0, ZERO, u, ngrid, (long)nao * ngrid, nset));
-    for (int k1 = 0; k1 < no; ++k1) {
-      const cplx* f1 = fo + (long)k1 * fo_ks;
-      double kq1[3], q[3], kd[3];
-      if (fbandv)
-        for (int d = 0; d < 3; ++d) kq1[d] = h_kband[3 * k1 + d];
-      else
-        kpoint(kmesh, g, k1, kq1);
-      for (int d = 0; d < 3; ++d) q[d] = kq2[d] - kq1[d];
-      for (int d = 0; d < 3; ++d) kd[d] = g.a[d][0] * q[0] + g.a[d][1] * q[1] + g.a[d][2] * q[2];
-      FISDF_TRY(coulg_weight(c->stream, mesh, g, q, 1.0 / (double)ngl, 0, w, omega));
-      for (int m0 = 0; m0 < nao; m0 += p.mc) {
-        const int m1 = std::min(nao, m0 + p.mc);
-        const int R = (m1 - m0) * nao;
-        FISDF_TRY(pair_density(c->stream, f1, f2, ngrid, nao, m0, m1, rows));
-        // vR conj(em)^-1 = ifft(coulG fft(pair em)) by the forward transform between conjugations;
-        // the second conjugation and conj(em) are the contraction's
-        FISDF_TRY(fft3d(c->stream, rows, ngl, nullptr, rows, ngl, R, mesh[0], mesh[1], mesh[2], kd,
-                        w, nullptr));
-        FISDF_TRY(conj_inplace(c->stream, rows, (long)R * ngl));
-        FISDF_TRY(fft3d(c->stream, rows, ngl, nullptr, rows, ngl, R, mesh[0], mesh[1], mesh[2],
-                        nullptr, nullptr, nullptr));
-        FISDF_TRY(exx_contract(c->stream, rows, u, f1, mesh, kd, m0, m1, nao, nset, scale,
-                               k2 > 0 ? 1 : 0, vk + (long)k1 * nn, (long)no * nn, part,
-                               part_elems));
-      }
-    }
-  }
-  return 0;
-}
-
-// ---- exact FFT-grid K, the occupied-orbital form (the kernels are in kfft_lr.hip) -------------
-int fisdf_kfft_lr_plan(int nao, long ngrid, int nset, int imax, long work_bytes, int* h_mc,
-                       int* h_nchunk, int* h_run_len, int* h_nrun, int* h_pair_tw, int* h_exx_sc,
-                       int* h_exx_nn, long* h_row_bytes, long* h_bytes) {
-  t_cur_ctx = nullptr;
-  FISDF_CHECK(nao >= 1 && nao <= kKfftMaxNao && ngrid >= 1 && ngrid < (1L << 31) && nset >= 1 &&
-                  nset <= kKfftMaxSets && imax >= 1 && imax <= kKfftMaxNao && work_bytes >= 0,
-              "kfft_lr_plan: bad sizes");
-  KfftLrPlan p;
-  kfft_lr_plan(nao, ngrid, nset, imax, work_bytes, &p);
-  if (h_mc) *h_mc = p.ok ? p.mc : 0;
-  if (h_nchunk) *h_nchunk = p.ok ? p.nchunk : 0;
-  if (h_run_len) *h_run_len = p.run_len;
-  if (h_nrun) *h_nrun = p.nrun;
-  if (h_pair_tw) *h_pair_tw = p.pair_tw;
-  if (h_exx_sc) *h_exx_sc = p.exx_sc;
-  if (h_exx_nn) *h_exx_nn = p.exx_nn;
-  if (h_row_bytes) *h_row_bytes = p.row_bytes;
-  if (h_bytes) *h_bytes = p.ok ? p.bytes : 0;
-  return 0;
 }
 
 int fisdf_pair_density_lr(fisdf_ctx* c, const void* f1v, int nao, const void* psiv, int ni,
@@ -3703,7 +3626,7 @@ int fisdf_exx_contract_lr(fisdf_ctx* c, const void* zv, const void* uv, const vo
   FISDF_CHECK(nao >= 1 && nset >= 1 && ni >= 1, "exx_contract_lr: sizes must be >= 1");
   FISDF_CHECK(0 <= m0 && m0 < m1 && m1 <= nao, "exx_contract_lr: bad row range");
   StageTimer tm(c, FISDF_ST_K);
-  const long we = exx_contract_lr_work_elems((int)ngl, nao, nset, m1 - m0);
+  const long we = exx_contract_work_elems((int)ngl, nao, nset, m1 - m0, kLrSetChunk);
   void* base;
   FISDF_TRY(arena_get(c, sizeof(cplx) * we, &base));
   return exx_contract_lr(c->stream, (const cplx*)zv, (const cplx*)uv, (const cplx*)f1v, mesh, h_kd,
@@ -3711,89 +3634,93 @@ int fisdf_exx_contract_lr(fisdf_ctx* c, const void* zv, const void* uv, const vo
                          (cplx*)base, we);
 }
 
-int fisdf_get_k_fft_lr(fisdf_ctx* c, const void* fv, long f_kstride, const int kmesh[3],
-                       const int mesh[3], const double a[9], int nao, const void* Av,
-                       const void* Bv, const int* h_rank, int rmax, int nset, double omega,
-                       const void* fbandv, const double* h_kband, int nband, long work_bytes,
-                       void* vkv) {
-  FISDF_TRY(device_guard(c));
-  FISDF_CHECK(fv && Av && Bv && h_rank && vkv && kmesh, "get_k_fft_lr: null pointer");
-  FISDF_CHECK(kmesh[0] >= 1 && kmesh[1] >= 1 && kmesh[2] >= 1, "get_k_fft_lr: bad k-mesh");
-  FISDF_CHECK(nao >= 1 && nao <= kKfftMaxNao, "get_k_fft_lr: nao must be in [1, 32768]");
-  FISDF_CHECK(nset <= kKfftMaxSets, "get_k_fft_lr: more than 1024 sets");
-  FISDF_CHECK(rmax >= 1 && rmax <= kKfftMaxNao, "get_k_fft_lr: rmax must be in [1, 32768]");
-  FISDF_CHECK(nband >= 0 && work_bytes >= 0 && std::isfinite(omega), "get_k_fft_lr: bad arguments");
+// What the driver hands a form's steps: the sizes it has checked and the arena it has carved
+struct KfftWork {
+  int nk = 0, ngrid = 0;
+  double scale = 0;  // of the contraction: cell volume / ngrid / nk
+  long vk_set = 0;   // set stride of d_vk
+  cplx *rows = nullptr, *psi = nullptr, *u = nullptr, *part = nullptr;
+  long part_elems = 0;
+};
+// What a form of the exact K gives the driver; every step returns 0 or an error code
+struct KfftForm {
+  const char* name;   // the entry's name, the prefix of the driver's messages
+  const char* row_m;  // what one row m holds, for the plan's refusal
+  bool lowrank;       // kfft_plan's form
+  // the entry's checks that need nk; *rows_max = the most rows per row m of any k2 (0: K = 0)
+  std::function<int(int nk, int* rows_max)> sizes;
+  // enqueues what the blocks of k2 share (w.u, w.psi); *rows = its rows per row m (0: no work)
+  std::function<int(const KfftWork& w, int k2, const cplx* f2, int* rows)> prepare;
+  // the pair densities of the rows [m0, m1) into w.rows, (m1 - m0) rows transform rows
+  std::function<int(const KfftWork& w, const cplx* f1, int m0, int m1, int rows)> pair;
+  // the transformed w.rows into the rows [m0, m1) of vk_k1
+  std::function<int(const KfftWork& w, int rows, const cplx* f1, const double* kd, int m0, int m1,
+                    int accumulate, cplx* vk_k1)> contract;
+};
+
+// fisdf_get_k_fft and fisdf_get_k_fft_lr behind their own argument checks: K[s][k1] = (1/nk) sum_k2
+// of the blocks (k2, k1), each block in chunks of plan.mc rows m as pair densities, the transform
+// pair between two conjugations, and the contraction.  The first k2 that has work overwrites d_vk,
+// the later ones add; when no k2 has any, K = 0 is written and nothing else is read.
+static int get_k_fft_run(fisdf_ctx* c, const KfftForm& form, const void* fv, long f_kstride,
+                         const int kmesh[3], const int mesh[3], const double a[9], int nao,
+                         int nset, double omega, const void* fbandv, const double* h_kband,
+                         int nband, long work_bytes, void* vkv) {
+  const std::string nm = std::string(form.name) + ": ";
+  FISDF_CHECK(kmesh[0] >= 1 && kmesh[1] >= 1 && kmesh[2] >= 1, nm + "bad k-mesh");
+  FISDF_CHECK(nao >= 1 && nao <= kKfftMaxNao, nm + "nao must be in [1, 32768]");
+  FISDF_CHECK(nset <= kKfftMaxSets, nm + "more than 1024 sets");
+  FISDF_CHECK(nband >= 0 && work_bytes >= 0 && std::isfinite(omega), nm + "bad arguments");
   FISDF_CHECK((fbandv != nullptr) == (nband > 0) && (fbandv == nullptr || h_kband != nullptr),
-              "get_k_fft_lr: band AOs, band k-points and nband go together");
+              nm + "band AOs, band k-points and nband go together");
   long ngl = 0;
   FISDF_TRY(potential_check(mesh, a, nset, &ngl));
   const long nkl = (long)kmesh[0] * kmesh[1] * kmesh[2];
-  FISDF_CHECK(nkl <= 65535, "get_k_fft_lr: more than 65535 k-points");
-  FISDF_CHECK(f_kstride >= ngl * nao, "get_k_fft_lr: f_kstride below ngrid * nao");
+  FISDF_CHECK(nkl <= 65535, nm + "more than 65535 k-points");
+  FISDF_CHECK(f_kstride >= ngl * nao, nm + "f_kstride below ngrid * nao");
   const int nk = (int)nkl, ngrid = (int)ngl;
-  long imax = 0;
-  for (int k = 0; k < nk; ++k) {
-    long ik = 0;
-    for (int s = 0; s < nset; ++s) {
-      const int r = h_rank[(long)s * nk + k];
-      FISDF_CHECK(r >= 0 && r <= rmax, "get_k_fft_lr: rank outside [0, rmax]");
-      ik += r;
-    }
-    imax = std::max(imax, ik);
-  }
-  FISDF_CHECK(imax <= kKfftMaxNao, "get_k_fft_lr: more than 32768 orbitals at one k-point");
+  int rows_max = 0;
+  FISDF_TRY(form.sizes(nk, &rows_max));
   const cplx* f = (const cplx*)fv;
-  const cplx* A = (const cplx*)Av;
-  const cplx* B = (const cplx*)Bv;
   cplx* vk = (cplx*)vkv;
   // K at the k-mesh from f itself, or at the band k-points from their AOs on the same grid
   const cplx* fo = fbandv ? (const cplx*)fbandv : f;
   const long fo_ks = fbandv ? ngl * nao : f_kstride;
   const int no = fbandv ? nband : nk;
-  const long nn = (long)nao * nao, nr = (long)nao * rmax;
-  StageTimer tm(c, FISDF_ST_K);
-  if (imax == 0) {  // no k2 has an orbital: K = 0 (nothing is transformed, the mesh is not read)
+  const long nn = (long)nao * nao;
+  if (rows_max == 0) {  // nothing is transformed, the mesh is not read
+    StageTimer tm(c, FISDF_ST_K);
     FISDF_HIP(hipMemsetAsync(vk, 0, sizeof(cplx) * (size_t)nset * no * nn, c->stream));
     return 0;
   }
-  KfftLrPlan p;
-  kfft_lr_plan(nao, ngl, nset, (int)imax, work_bytes, &p);
-  FISDF_CHECK(p.ok, "get_k_fft_lr: work_bytes below one row of m (the transform rows of the "
-                    "orbitals of the fullest k-point)");
+  KfftPlan p;
+  kfft_plan(nao, ngl, nset, rows_max, form.lowrank, work_bytes, &p);
+  FISDF_CHECK(p.ok, nm + "work_bytes below one row of m (" + form.row_m + ")");
   // fft3d makes its own checks of the mesh when the first transform is reached: until then only
   // the arena is written, and d_vk is first written behind both transforms of the first block
   CellGeom g;
   lattice(a, g);
+  StageTimer tm(c, FISDF_ST_K);
   void* base;
   FISDF_TRY(arena_get(c, (size_t)p.bytes, &base));
-  cplx* rows = (cplx*)((char*)base + p.off_rows);
-  cplx* psi = (cplx*)((char*)base + p.off_psi);
-  cplx* u = (cplx*)((char*)base + p.off_u);
-  double* w = (double*)((char*)base + p.off_w);
-  cplx* part = (cplx*)((char*)base + p.off_part);
-  const long part_elems = exx_contract_lr_work_elems(ngrid, nao, nset, p.mc);
-  const double scale = cell_volume(a) / (double)ngl / (double)nk;
-  std::vector<int> seg(nset + 1);
-  bool first = true;  // the first k2 that has work overwrites d_vk, the later ones add
+  KfftWork w;
+  w.nk = nk;
+  w.ngrid = ngrid;
+  w.scale = cell_volume(a) / (double)ngl / (double)nk;
+  w.vk_set = (long)no * nn;
+  w.rows = (cplx*)((char*)base + p.off_rows);
+  w.psi = (cplx*)((char*)base + p.off_psi);
+  w.u = (cplx*)((char*)base + p.off_u);
+  w.part = (cplx*)((char*)base + p.off_part);
+  w.part_elems = p.part_elems;
+  double* wt = (double*)((char*)base + p.off_w);
+  bool first = true;  // no k2 has written d_vk yet
   for (int k2 = 0; k2 < nk; ++k2) {
-    seg[0] = 0;
-    for (int s = 0; s < nset; ++s) seg[s + 1] = seg[s] + h_rank[(long)s * nk + k2];
-    const int ni = seg[nset];
-    if (ni == 0) continue;
-    const cplx* f2 = f + (long)k2 * f_kstride;
+    int rows = 0;
+    FISDF_TRY(form.prepare(w, k2, f + (long)k2 * f_kstride, &rows));
+    if (rows == 0) continue;
     double kq2[3];
     kpoint(kmesh, g, k2, kq2);
-    // the orbitals of every set on the grid: psi[:, segment s] = f_k2 A[s][k2][:, :r_s], (ngrid,
-    // ni), and u[segment s] = (B[s][k2][:, :r_s])^H f_k2^H = conj(psiB)^T, (ni, ngrid)
-    for (int s = 0; s < nset; ++s) {
-      const int r = seg[s + 1] - seg[s];
-      if (r == 0) continue;
-      const long sk = ((long)s * nk + k2) * nr;
-      FISDF_TRY(zgemm(c->stream, OP_N, OP_N, ngrid, r, nao, ONE, f2, nao, 0, A + sk, rmax, 0, ZERO,
-                      psi + seg[s], ni, 0, 1));
-      FISDF_TRY(zgemm(c->stream, OP_C, OP_C, r, ngrid, nao, ONE, B + sk, rmax, 0, f2, nao, 0, ZERO,
-                      u + (long)seg[s] * ngrid, ngrid, 0, 1));
-    }
     for (int k1 = 0; k1 < no; ++k1) {
       const cplx* f1 = fo + (long)k1 * fo_ks;
       double kq1[3], q[3], kd[3];
@@ -3803,25 +3730,121 @@ int fisdf_get_k_fft_lr(fisdf_ctx* c, const void* fv, long f_kstride, const int k
         kpoint(kmesh, g, k1, kq1);
       for (int d = 0; d < 3; ++d) q[d] = kq2[d] - kq1[d];
       for (int d = 0; d < 3; ++d) kd[d] = g.a[d][0] * q[0] + g.a[d][1] * q[1] + g.a[d][2] * q[2];
-      FISDF_TRY(coulg_weight(c->stream, mesh, g, q, 1.0 / (double)ngl, 0, w, omega));
+      FISDF_TRY(coulg_weight(c->stream, mesh, g, q, 1.0 / (double)ngl, 0, wt, omega));
       for (int m0 = 0; m0 < nao; m0 += p.mc) {
         const int m1 = std::min(nao, m0 + p.mc);
-        const int R = (m1 - m0) * ni;
-        FISDF_TRY(pair_density_lr(c->stream, f1, nao, psi, ni, ni, ngrid, m0, m1, rows));
-        // the transform pair of the dm form (fisdf_get_k_fft) over (m1 - m0) ni rows
-        FISDF_TRY(fft3d(c->stream, rows, ngl, nullptr, rows, ngl, R, mesh[0], mesh[1], mesh[2], kd,
-                        w, nullptr));
-        FISDF_TRY(conj_inplace(c->stream, rows, (long)R * ngl));
-        FISDF_TRY(fft3d(c->stream, rows, ngl, nullptr, rows, ngl, R, mesh[0], mesh[1], mesh[2],
+        const int R = (m1 - m0) * rows;
+        FISDF_TRY(form.pair(w, f1, m0, m1, rows));
+        // vR conj(em)^-1 = ifft(coulG fft(pair em)) by the forward transform between conjugations;
+        // the second conjugation and conj(em) are the contraction's
+        FISDF_TRY(fft3d(c->stream, w.rows, ngl, nullptr, w.rows, ngl, R, mesh[0], mesh[1], mesh[2],
+                        kd, wt, nullptr));
+        FISDF_TRY(conj_inplace(c->stream, w.rows, (long)R * ngl));
+        FISDF_TRY(fft3d(c->stream, w.rows, ngl, nullptr, w.rows, ngl, R, mesh[0], mesh[1], mesh[2],
                         nullptr, nullptr, nullptr));
-        FISDF_TRY(exx_contract_lr(c->stream, rows, u, f1, mesh, kd, m0, m1, nao, ni, seg.data(),
-                                  nset, scale, first ? 0 : 1, vk + (long)k1 * nn, (long)no * nn,
-                                  part, part_elems));
+        FISDF_TRY(form.contract(w, rows, f1, kd, m0, m1, first ? 0 : 1, vk + (long)k1 * nn));
       }
     }
     first = false;
   }
   return 0;
+}
+
+int fisdf_get_k_fft(fisdf_ctx* c, const void* fv, long f_kstride, const int kmesh[3],
+                    const int mesh[3], const double a[9], int nao, const void* dmsv, int nset,
+                    double omega, const void* fbandv, const double* h_kband, int nband,
+                    long work_bytes, void* vkv) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(fv && dmsv && vkv && kmesh, "get_k_fft: null pointer");
+  const cplx* dms = (const cplx*)dmsv;
+  const long nn = (long)nao * nao;
+  const cplx* f2 = nullptr;  // of the k2 prepared last
+  KfftForm form;
+  form.name = "get_k_fft";
+  form.row_m = "nao transform rows of the grid";
+  form.lowrank = false;
+  form.sizes = [&](int, int* rows_max) {
+    *rows_max = nao;
+    return 0;
+  };
+  // u_s = D[s][k2] f_k2^H, (nset, nao, ngrid): every k2 has work
+  form.prepare = [&](const KfftWork& w, int k2, const cplx* fk2, int* rows) {
+    f2 = fk2;
+    *rows = nao;
+    return zgemm(c->stream, OP_N, OP_C, nao, w.ngrid, nao, ONE, dms + (long)k2 * nn, nao,
+                 (long)w.nk * nn, f2, nao, 0, ZERO, w.u, w.ngrid, (long)nao * w.ngrid, nset);
+  };
+  form.pair = [&](const KfftWork& w, const cplx* f1, int m0, int m1, int) {
+    return pair_density(c->stream, f1, f2, w.ngrid, nao, m0, m1, w.rows);
+  };
+  form.contract = [&](const KfftWork& w, int, const cplx* f1, const double* kd, int m0, int m1,
+                      int accumulate, cplx* vk_k1) {
+    return exx_contract(c->stream, w.rows, w.u, f1, mesh, kd, m0, m1, nao, nset, w.scale,
+                        accumulate, vk_k1, w.vk_set, w.part, w.part_elems);
+  };
+  return get_k_fft_run(c, form, fv, f_kstride, kmesh, mesh, a, nao, nset, omega, fbandv, h_kband,
+                       nband, work_bytes, vkv);
+}
+
+int fisdf_get_k_fft_lr(fisdf_ctx* c, const void* fv, long f_kstride, const int kmesh[3],
+                       const int mesh[3], const double a[9], int nao, const void* Av,
+                       const void* Bv, const int* h_rank, int rmax, int nset, double omega,
+                       const void* fbandv, const double* h_kband, int nband, long work_bytes,
+                       void* vkv) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(fv && Av && Bv && h_rank && vkv && kmesh, "get_k_fft_lr: null pointer");
+  FISDF_CHECK(rmax >= 1 && rmax <= kKfftMaxNao, "get_k_fft_lr: rmax must be in [1, 32768]");
+  const cplx* A = (const cplx*)Av;
+  const cplx* B = (const cplx*)Bv;
+  const long nr = (long)nao * rmax;
+  std::vector<int> seg;  // of the k2 prepared last: set s owns the rows [seg[s], seg[s + 1])
+  KfftForm form;
+  form.name = "get_k_fft_lr";
+  form.row_m = "the transform rows of the orbitals of the fullest k-point";
+  form.lowrank = true;
+  form.sizes = [&](int nk, int* rows_max) {
+    long imax = 0;
+    for (int k = 0; k < nk; ++k) {
+      long ik = 0;
+      for (int s = 0; s < nset; ++s) {
+        const int r = h_rank[(long)s * nk + k];
+        FISDF_CHECK(r >= 0 && r <= rmax, "get_k_fft_lr: rank outside [0, rmax]");
+        ik += r;
+      }
+      imax = std::max(imax, ik);
+    }
+    FISDF_CHECK(imax <= kKfftMaxNao, "get_k_fft_lr: more than 32768 orbitals at one k-point");
+    *rows_max = (int)imax;
+    seg.resize(nset + 1);
+    return 0;
+  };
+  // the orbitals of every set on the grid: psi[:, segment s] = f_k2 A[s][k2][:, :r_s], (ngrid,
+  // ni), and u[segment s] = (B[s][k2][:, :r_s])^H f_k2^H = conj(psiB)^T, (ni, ngrid)
+  form.prepare = [&](const KfftWork& w, int k2, const cplx* f2, int* rows) {
+    seg[0] = 0;
+    for (int s = 0; s < nset; ++s) seg[s + 1] = seg[s] + h_rank[(long)s * w.nk + k2];
+    const int ni = *rows = seg[nset];
+    for (int s = 0; s < nset; ++s) {
+      const int r = seg[s + 1] - seg[s];
+      if (r == 0) continue;
+      const long sk = ((long)s * w.nk + k2) * nr;
+      FISDF_TRY(zgemm(c->stream, OP_N, OP_N, w.ngrid, r, nao, ONE, f2, nao, 0, A + sk, rmax, 0,
+                      ZERO, w.psi + seg[s], ni, 0, 1));
+      FISDF_TRY(zgemm(c->stream, OP_C, OP_C, r, w.ngrid, nao, ONE, B + sk, rmax, 0, f2, nao, 0,
+                      ZERO, w.u + (long)seg[s] * w.ngrid, w.ngrid, 0, 1));
+    }
+    return 0;
+  };
+  form.pair = [&](const KfftWork& w, const cplx* f1, int m0, int m1, int ni) {
+    return pair_density_lr(c->stream, f1, nao, w.psi, ni, ni, w.ngrid, m0, m1, w.rows);
+  };
+  form.contract = [&](const KfftWork& w, int ni, const cplx* f1, const double* kd, int m0, int m1,
+                      int accumulate, cplx* vk_k1) {
+    return exx_contract_lr(c->stream, w.rows, w.u, f1, mesh, kd, m0, m1, nao, ni, seg.data(), nset,
+                           w.scale, accumulate, vk_k1, w.vk_set, w.part, w.part_elems);
+  };
+  return get_k_fft_run(c, form, fv, f_kstride, kmesh, mesh, a, nao, nset, omega, fbandv, h_kband,
+                       nband, work_bytes, vkv);
 }
 
 // ---- A8 -----------------------------------------------------------------------

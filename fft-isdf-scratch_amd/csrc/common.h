@@ -83,6 +83,20 @@ __host__ __device__ inline cplx csub(cplx a, cplx b) { return cmk(a.x - b.x, a.y
 __host__ __device__ inline cplx cmul(cplx a, cplx b) { return cmk(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __host__ __device__ inline cplx cconj(cplx a) { return cmk(a.x, -a.y); }
 __host__ __device__ inline cplx cscale(cplx a, double s) { return cmk(a.x * s, a.y * s); }
+// acc += a b as four fused multiply-adds
+__device__ __forceinline__ void cfma(cplx& acc, cplx a, cplx b) {
+  acc.x = fma(a.x, b.x, acc.x);
+  acc.x = fma(-a.y, b.y, acc.x);
+  acc.y = fma(a.x, b.y, acc.y);
+  acc.y = fma(a.y, b.x, acc.y);
+}
+// acc += conj(a) b
+__device__ __forceinline__ void cfma_conj(cplx& acc, cplx a, cplx b) {
+  acc.x = fma(a.x, b.x, acc.x);
+  acc.x = fma(a.y, b.y, acc.x);
+  acc.y = fma(a.x, b.y, acc.y);
+  acc.y = fma(-a.y, b.x, acc.y);
+}
 
 // ---- GEMM op codes: bit0 = transpose, bit1 = conjugate
 enum Op { OP_N = 0, OP_T = 1, OP_R = 2 /*conj only*/, OP_C = 3 /*conj-transpose*/ };

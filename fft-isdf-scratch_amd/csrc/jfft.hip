@@ -12,14 +12,6 @@ namespace fisdf {
 
 namespace {
 
-// acc += a b as four fused multiply-adds
-__device__ __forceinline__ void cfma(cplx& acc, cplx a, cplx b) {
-  acc.x = fma(a.x, b.x, acc.x);
-  acc.x = fma(-a.y, b.y, acc.x);
-  acc.y = fma(a.x, b.y, acc.y);
-  acc.y = fma(a.y, b.x, acc.y);
-}
-
 // ---- rho[s][g] = (1/nk) sum_k sum_mn f_k[g,m] D_sk[m,n] conj(f_k[g,n]) ----------------------
 // A workgroup of 256 threads owns PG * 64 grid points and loops over k.  Per k it stages the
 // points' f rows (row pitch odd in 16-byte units: the rows are nao * 16 B apart, so lanes of

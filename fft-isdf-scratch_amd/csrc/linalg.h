@@ -201,25 +201,28 @@ int weighted_gram(hipStream_t s, const cplx* f, long fks, int nk, int ngrid, int
 // a[e] = conj(a[e]): ifft(x) = conj(fft(conj(x))) / N around the forward fft3d
 int conj_inplace(hipStream_t s, cplx* a, long n);
 
-// ---- exact FFT-grid K (kfft.hip; PySCF fft_jk.get_k_kpts, the dm form) ----
-constexpr int kKfftGT = 64;        // grid points per tile of both kernels (one per lane)
+// ---- exact FFT-grid K (kfft.hip; PySCF fft_jk.get_k_kpts) in its two forms: the dm form, nao
+// transform rows per row m, and the occupied-orbital (low-rank) form below ----
+constexpr int kKfftGT = 64;        // grid points per tile of the kernels (one per lane)
 constexpr int kExxMT = 8;          // rows m per workgroup of the contraction
 constexpr int kExxNT = 32;         // output columns per n-tile of the contraction
 constexpr long kExxRuns = 128;     // grid runs the contraction aims at
 constexpr long kKfftWorkBytes = 1L << 29;  // default budget of the transform rows
 constexpr int kKfftMaxNao = 1 << 15, kKfftMaxSets = 1 << 10;  // kfft_plan's arithmetic fits a long
 // P[(m - m0) nao + l][g] = conj(f1[g,m]) f2[g,l] for m in [m0, m1): (m1 - m0) nao rows of ngrid,
-// f1 and f2 (ngrid, nao).  pair_density_variant: the AO tile width of the instantiation (8, 32)
+// f1 and f2 (ngrid, nao): pair_density_lr with psi = f2, ni = ld = nao.  pair_density_variant: the
+// tile width of the instantiation (8, 32) for ni rows per row m
 int pair_density(hipStream_t s, const cplx* f1, const cplx* f2, int ngrid, int nao, int m0, int m1,
                  cplx* P);
-int pair_density_variant(int nao);
+int pair_density_variant(int ni);
 // vk[s][m][n] (+)= scale sum_g t_s[m,g] f1[g,n] for m in [m0, m1), with
 // t_s[m,g] = exp(+i frac(g).kd) sum_l conj(Z[(m - m0) nao + l][g]) u[s][l][g] (kd null: no phase;
 // frac the fftfreq fractions of fft3d's phase); Z (m1 - m0) nao rows of ngrid, u (nset, nao,
 // ngrid), vk set stride vk_set.  The grid is split into *nrun runs of *run_len points
 // (exx_grid_split, from the shape only) whose partial blocks are summed in run order; at most
 // kJfftSetChunk sets per pass over Z.  accumulate = 0 overwrites the rows.  work:
-// exx_contract_work_elems complex elements.  exx_contract_variant: the n-tiles per thread of the
+// exx_contract_work_elems complex elements (set_chunk: the sets per launch of the form, this one's
+// kJfftSetChunk).  exx_contract_variant: the n-tiles per thread of the
 // instantiation (1, 2, 4); nao > 128 runs the last once per group of 128 columns, each of which
 // reads Z again
 int exx_contract(hipStream_t s, const cplx* Z, const cplx* u, const cplx* f1, const int mesh[3],
@@ -227,54 +230,46 @@ int exx_contract(hipStream_t s, const cplx* Z, const cplx* u, const cplx* f1, co
                  cplx* vk, long vk_set, cplx* work, long work_elems);
 int exx_contract_variant(int nao);
 void exx_grid_split(int ngrid, int nao, int nset, int* run_len, int* nrun);
-long exx_contract_work_elems(int ngrid, int nao, int nset, int mc);
-// What fisdf_get_k_fft does for given sizes and a byte budget for the transform rows (0: the
-// default kKfftWorkBytes; never more than nao rows m): ok = 0 when the budget is below one row m
-// (row_bytes = nao transform rows) or a size is out of range (nao > kKfftMaxNao, nset >
-// kKfftMaxSets, ngrid >= 2^31).  mc rows m per chunk,
-// nchunk chunks; the arena's layout (byte offsets) and total.
-struct KfftPlan {
-  int ok = 0;
-  int mc = 0, nchunk = 0;
-  int run_len = 0, nrun = 0;
-  int pair_tw = 0, exx_nn = 0;
-  long row_bytes = 0;
-  long off_rows = 0, off_u = 0, off_w = 0, off_part = 0, bytes = 0;
-};
-void kfft_plan(int nao, long ngrid, int nset, long work_bytes, KfftPlan* p);
+long exx_contract_work_elems(int ngrid, int nao, int nset, int mc, int set_chunk);
 
-// ---- exact FFT-grid K, the occupied-orbital (low-rank) form (kfft_lr.hip) ----
-// D[s][k2] = A B^H with r_s columns: the orbitals of all sets stacked, ni = sum_s r_s rows per row
-// m where the dm form has nao, set s owning the segment [seg[s], seg[s + 1]).
+// The occupied-orbital (low-rank) form: D[s][k2] = A B^H with r_s columns, the orbitals of all
+// sets stacked, ni = sum_s r_s rows per row m where the dm form has nao, set s owning the segment
+// [seg[s], seg[s + 1]).
 constexpr int kLrRows = 32;     // rows (set, m) per workgroup of the segmented contraction
 constexpr int kLrSetChunk = 2;  // sets per launch: 32 rows m per workgroup for one set, 16 for two
 // P[(m - m0) ni + i][g] = conj(f1[g,m]) psi[g,i] for m in [m0, m1): f1 (ngrid, nao), psi (ngrid,
-// ni) at leading dimension ld.  pair_density_lr_variant: the orbital tile width (8, 32)
+// ni) at leading dimension ld.  The tile width is pair_density_variant(ni)
 int pair_density_lr(hipStream_t s, const cplx* f1, int nao, const cplx* psi, int ni, long ld,
                     int ngrid, int m0, int m1, cplx* P);
-int pair_density_lr_variant(int ni);
 // vk[s][m][n] (+)= scale sum_g t_s[m,g] f1[g,n] for m in [m0, m1), with
 // t_s[m,g] = exp(+i frac(g).kd) sum_{i in segment s} conj(Z[(m - m0) ni + i][g]) u[i][g]; Z
 // (m1 - m0) ni rows of ngrid, u (ni, ngrid), seg nset + 1 host offsets from 0 to ni (an empty
 // segment gives zeros).  Runs, reduction, accumulate and vk_set as exx_contract; at most
 // kLrSetChunk sets per launch, each launch reading only its sets' rows of Z.  work:
-// exx_contract_lr_work_elems complex elements.  The n-tiles per thread are exx_contract_variant's
+// exx_contract_work_elems complex elements at set_chunk = kLrSetChunk.  The n-tiles per thread are
+// exx_contract_variant's
 int exx_contract_lr(hipStream_t s, const cplx* Z, const cplx* u, const cplx* f1, const int mesh[3],
                     const double* kd, int m0, int m1, int nao, int ni, const int* seg, int nset,
                     double scale, int accumulate, cplx* vk, long vk_set, cplx* work,
                     long work_elems);
-long exx_contract_lr_work_elems(int ngrid, int nao, int nset, int mc);
-// What fisdf_get_k_fft_lr does for given sizes, imax the largest ni of a k2, and a byte budget for
-// the transform rows (0: kKfftWorkBytes): as KfftPlan with row_bytes = imax transform rows; the
-// arena also holds the orbitals on the grid (psi and u, imax rows each).
-struct KfftLrPlan {
+
+// What fisdf_get_k_fft (rows = nao, lowrank = false) and fisdf_get_k_fft_lr (rows = imax, the
+// largest ni of a k2, lowrank = true) do for given sizes and a byte budget for the transform rows
+// (0: the default kKfftWorkBytes; never more than nao rows m): ok = 0 when the budget is below one
+// row m (row_bytes = its `rows` transform rows; mc, nchunk and bytes are then 0) or a size is out
+// of range (nao or rows > kKfftMaxNao, nset > kKfftMaxSets, ngrid >= 2^31).  mc rows m per chunk,
+// nchunk chunks; exx_sc the most sets per contraction launch (the form's set chunk); the arena's
+// layout (byte offsets) and total.  The dm form's u is (nset, nao, ngrid) and it has no psi (its
+// slot is empty); the low-rank form's psi and u hold the orbitals on the grid, `rows` rows each.
+struct KfftPlan {
   int ok = 0;
   int mc = 0, nchunk = 0;
   int run_len = 0, nrun = 0;
   int pair_tw = 0, exx_sc = 0, exx_nn = 0;
-  long row_bytes = 0;
+  long row_bytes = 0, part_elems = 0;
   long off_rows = 0, off_psi = 0, off_u = 0, off_w = 0, off_part = 0, bytes = 0;
 };
-void kfft_lr_plan(int nao, long ngrid, int nset, int imax, long work_bytes, KfftLrPlan* p);
+void kfft_plan(int nao, long ngrid, int nset, int rows, bool lowrank, long work_bytes,
+               KfftPlan* p);
 
 }  // namespace fisdf

@@ -1,5 +1,5 @@
 """Cases, restated rules and references for the exact FFT-grid K in the occupied-orbital (low-rank)
-form (csrc/kfft_lr.hip and its entries in api.hip; ISDF.k_form = "lowrank"): the pair builder
+form (csrc/kfft.hip and its entries in api.hip; ISDF.k_form = "lowrank"): the pair builder
 against the orbitals on the grid, the segmented contraction and the whole fisdf_get_k_fft_lr.  No
 tests and no GPU here: tests/test_kfft_lr_cases.py checks this file on the CPU,
 tests/test_gpu_kfft_lr.py runs the device against it.  Everything shared with the dm form — the

@@ -17,10 +17,10 @@ import pytest
 
 import kfft_cases as K
 from cases import inputs
+from kfft_gpu import edges_intact, env, f_view, nan_view, out_view  # noqa: F401 (env: a fixture)
 
 pytestmark = pytest.mark.gpu
 
-NAN = complex(np.nan, np.nan)
 RATIO = {}
 
 
@@ -35,53 +35,6 @@ def report():
 def note(family, err, tol):
     RATIO[family] = max(RATIO.get(family, 0.0), err / tol)
     print(f"  [{family}] err/bound {err / tol:.3f}, largest so far {RATIO[family]:.3f}")
-
-
-@pytest.fixture(scope="module")
-def env():
-    import torch
-    from fisdf import _lib
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    ctx = _lib.Context(0, torch.cuda.current_stream().cuda_stream)
-    return torch, _lib, ctx
-
-
-def dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def nan_view(torch, a):
-    """a (flat) on the device inside NaN: (buffer, view of the logical part)."""
-    a = np.asarray(a, complex).ravel()
-    buf = np.full(a.size + 2 * K.EDGE, NAN)
-    buf[K.EDGE:K.EDGE + a.size] = a
-    d = dev(torch, buf)
-    return d, d[K.EDGE:K.EDGE + a.size]
-
-
-def f_view(torch, f):
-    """f (nk, ngrid, nao) with its k blocks f_kstride apart in NaN: (buffer, view, f_kstride)."""
-    nk, ngrid, nao = f.shape
-    ks = ngrid * nao + K.KPAD
-    buf = np.full(nk * ks + 2 * K.EDGE, NAN)
-    for k in range(nk):
-        buf[K.EDGE + k * ks: K.EDGE + k * ks + ngrid * nao] = f[k].ravel()
-    d = dev(torch, buf)
-    return d, d[K.EDGE:], ks
-
-
-def out_view(torch, n, fill=None):
-    """n output elements inside the sentinel, themselves the sentinel or `fill`."""
-    buf = np.full(n + 2 * K.EDGE, K.SENTINEL)
-    if fill is not None:
-        buf[K.EDGE:K.EDGE + n] = np.asarray(fill).ravel()
-    d = dev(torch, buf)
-    return d, d[K.EDGE:K.EDGE + n]
-
-
-def edges_intact(d, n):
-    h = d.cpu().numpy()
-    return bool(np.all(h[:K.EDGE] == K.SENTINEL) and np.all(h[K.EDGE + n:] == K.SENTINEL))
 
 
 # ---- the pair-density builder ---------------------------------------------------------------------

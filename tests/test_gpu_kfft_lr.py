@@ -16,10 +16,10 @@ import pytest
 import kfft_cases as K
 import kfft_lr_cases as R
 from cases import inputs
+from kfft_gpu import NAN, edges_intact, env, f_view, nan_view, out_view  # noqa: F401 (env: a fixture)
 
 pytestmark = pytest.mark.gpu
 
-NAN = complex(np.nan, np.nan)
 RATIO = {}
 
 
@@ -34,53 +34,6 @@ def report():
 def note(family, err, tol):
     RATIO[family] = max(RATIO.get(family, 0.0), err / tol)
     print(f"  [{family}] err/bound {err / tol:.3f}, largest so far {RATIO[family]:.3f}")
-
-
-@pytest.fixture(scope="module")
-def env():
-    import torch
-    from fisdf import _lib
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    ctx = _lib.Context(0, torch.cuda.current_stream().cuda_stream)
-    return torch, _lib, ctx
-
-
-def dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def nan_view(torch, a):
-    """a (flat) on the device inside NaN: (buffer, view of the logical part)."""
-    a = np.asarray(a, complex).ravel()
-    buf = np.full(a.size + 2 * K.EDGE, NAN)
-    buf[K.EDGE:K.EDGE + a.size] = a
-    d = dev(torch, buf)
-    return d, d[K.EDGE:K.EDGE + a.size]
-
-
-def f_view(torch, f):
-    """f (nk, ngrid, nao) with its k blocks f_kstride apart in NaN: (buffer, view, f_kstride)."""
-    nk, ngrid, nao = f.shape
-    ks = ngrid * nao + K.KPAD
-    buf = np.full(nk * ks + 2 * K.EDGE, NAN)
-    for k in range(nk):
-        buf[K.EDGE + k * ks: K.EDGE + k * ks + ngrid * nao] = f[k].ravel()
-    d = dev(torch, buf)
-    return d, d[K.EDGE:], ks
-
-
-def out_view(torch, n, fill=None):
-    """n output elements inside the sentinel, themselves the sentinel or `fill`."""
-    buf = np.full(n + 2 * K.EDGE, K.SENTINEL)
-    if fill is not None:
-        buf[K.EDGE:K.EDGE + n] = np.asarray(fill).ravel()
-    d = dev(torch, buf)
-    return d, d[K.EDGE:K.EDGE + n]
-
-
-def edges_intact(d, n):
-    h = d.cpu().numpy()
-    return bool(np.all(h[:K.EDGE] == K.SENTINEL) and np.all(h[K.EDGE + n:] == K.SENTINEL))
 
 
 # ---- the pair builder -----------------------------------------------------------------------------
@@ -118,6 +71,29 @@ def test_pair_density_lr(env, c):
             assert bad < 0 and ctx.lib.fisdf_last_error(ctx.h)
         ctx.call("fisdf_sync")
         assert np.array_equal(ob.cpu().numpy(), before)
+
+
+def test_pair_density_is_the_lr_builder_on_f2(env):
+    """fisdf_pair_density(f1, f2) and fisdf_pair_density_lr(f1, nao, psi = f2, ni = nao, ld = nao)
+    write the same bits: the dm form's builder is the general one at that point, which is what lets
+    kfft.hip keep a single pair kernel."""
+    torch, L, ctx = env
+    for c in K.PAIR_CASES:
+        f1, f2 = K.pair_inputs(c)
+        b1, v1 = nan_view(torch, f1)
+        b2, v2 = (b1, v1) if c.same else nan_view(torch, f2)
+        n = c.nao * c.nao * c.ngrid
+        for m0, m1 in K.row_ranges(c.nao):
+            lo = m0 * c.nao * c.ngrid
+            ob, ov = out_view(torch, n)
+            ctx.call("fisdf_pair_density", L.ptr(v1), L.ptr(v2), c.ngrid, c.nao, m0, m1,
+                     L.ptr(ov[lo:]))
+            rb, rv = out_view(torch, n)
+            ctx.call("fisdf_pair_density_lr", L.ptr(v1), c.nao, L.ptr(v2), c.nao, c.nao, c.ngrid,
+                     m0, m1, L.ptr(rv[lo:]))
+            ctx.call("fisdf_sync")
+            assert edges_intact(ob, n) and edges_intact(rb, n)
+            assert np.array_equal(ov.cpu().numpy(), rv.cpu().numpy()), (K.pair_id(c), m0, m1)
 
 
 # ---- the segmented contraction --------------------------------------------------------------------
