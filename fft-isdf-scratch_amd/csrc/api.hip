@@ -3847,6 +3847,112 @@ int fisdf_get_k_fft_lr(fisdf_ctx* c, const void* fv, long f_kstride, const int k
                        nband, work_bytes, vkv);
 }
 
+// ---- exact FFT-grid four-index integrals (PySCF FFTDF.get_eri / ao2mo); the B builder and the
+// plan are in erifft.hip ---------------------------------------------------------------------------
+int fisdf_eri_fft_plan(int n1, int n2, int n3, int n4, int npair, long ngrid, long work_bytes,
+                       int* h_mc, int* h_nrow_chunks, int* h_bc, int* h_nb_chunks, int* h_b_once,
+                       int* h_tw, int* h_ksplit, long* h_bytes) {
+  t_cur_ctx = nullptr;
+  FISDF_CHECK(n1 >= 1 && n2 >= 1 && n3 >= 1 && n4 >= 1 && n1 <= kKfftMaxNao &&
+                  n2 <= kKfftMaxNao && n3 <= kKfftMaxNao && n4 <= kKfftMaxNao && npair >= 1 &&
+                  npair <= kEriMaxPairs && ngrid >= 1 && ngrid < (1L << 31) && work_bytes >= 0,
+              "eri_fft_plan: bad sizes");
+  EriFftPlan p;
+  eri_fft_plan(n1, n2, n3, n4, npair, ngrid, work_bytes, &p);
+  if (h_mc) *h_mc = p.mc;
+  if (h_nrow_chunks) *h_nrow_chunks = p.nrow_chunks;
+  if (h_bc) *h_bc = p.bc;
+  if (h_nb_chunks) *h_nb_chunks = p.nb_chunks;
+  if (h_b_once) *h_b_once = p.b_once;
+  if (h_tw) *h_tw = p.tw;
+  if (h_ksplit) *h_ksplit = p.ksplit;
+  if (h_bytes) *h_bytes = p.bytes;
+  return 0;
+}
+
+int fisdf_pair34(fisdf_ctx* c, const void* const* a3v, const void* const* a4v, int npair, int n3,
+                 int n4, long ld3, long ld4, const int mesh[3], const double* h_kd, int r0, int r1,
+                 void* outv) {
+  FISDF_TRY(device_guard(c));
+  StageTimer tm(c, FISDF_ST_K);
+  return pair34(c->stream, (const cplx* const*)a3v, (const cplx* const*)a4v, npair, n3, n4, ld3,
+                ld4, mesh, h_kd, r0, r1, (cplx*)outv);
+}
+
+// eri[p] = (vol/ngrid) conj(Z) B_p^T in chunks of plan.mc rows i: the pair densities of (a1, a2),
+// the transform pair between two conjugations as in get_k_fft_run, then one GEMM per (B chunk,
+// pair) straight into d_out — conj(Z) is the GEMM's op, conj(em) is in B
+int fisdf_get_eri_fft(fisdf_ctx* c, const int mesh[3], const double a[9], const double h_q[3],
+                      double omega, const void* a1v, int n1, const void* a2v, int n2,
+                      const void* const* a3v, const void* const* a4v, int npair, int n3, int n4,
+                      long work_bytes, void* outv) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(mesh && a && h_q && a1v && a2v && a3v && a4v && outv, "get_eri_fft: null pointer");
+  FISDF_CHECK(n1 >= 1 && n2 >= 1 && n3 >= 1 && n4 >= 1 && npair >= 1,
+              "get_eri_fft: sizes must be >= 1");
+  FISDF_CHECK(n1 <= kKfftMaxNao && n2 <= kKfftMaxNao && n3 <= kKfftMaxNao && n4 <= kKfftMaxNao,
+              "get_eri_fft: more than 32768 orbitals");
+  FISDF_CHECK(npair <= kEriMaxPairs, "get_eri_fft: more than 65535 pairs");
+  FISDF_CHECK(work_bytes >= 0 && std::isfinite(omega) && std::isfinite(h_q[0]) &&
+                  std::isfinite(h_q[1]) && std::isfinite(h_q[2]),
+              "get_eri_fft: bad arguments");
+  const cplx* const* a3 = (const cplx* const*)a3v;
+  const cplx* const* a4 = (const cplx* const*)a4v;
+  for (int p = 0; p < npair; ++p) FISDF_CHECK(a3[p] && a4[p], "get_eri_fft: null pair pointer");
+  long ngl = 0;
+  FISDF_TRY(potential_check(mesh, a, 1, &ngl));
+  EriFftPlan p;
+  eri_fft_plan(n1, n2, n3, n4, npair, ngl, work_bytes, &p);
+  FISDF_CHECK(p.ok, "get_eri_fft: work_bytes below one row (n2 transform rows or n4 rows of B)");
+  // fft3d makes its own checks of the mesh when the first transform is reached: until then only
+  // the arena is written, and d_out is first written behind both transforms of the first chunk
+  CellGeom g;
+  lattice(a, g);
+  StageTimer tm(c, FISDF_ST_K);
+  void* base;
+  FISDF_TRY(arena_get(c, (size_t)p.bytes, &base));
+  cplx* rows = (cplx*)((char*)base + p.off_rows);
+  cplx* B = (cplx*)((char*)base + p.off_b);
+  double* wt = (double*)((char*)base + p.off_w);
+  cplx* work = p.ksplit > 1 ? (cplx*)((char*)base + p.off_work) : nullptr;
+  const int ngrid = (int)ngl;
+  double kd[3];
+  for (int d = 0; d < 3; ++d) kd[d] = g.a[d][0] * h_q[0] + g.a[d][1] * h_q[1] + g.a[d][2] * h_q[2];
+  // q = 0: em = 1, neither the transform nor B carries a phase
+  const double* kdp = h_q[0] == 0 && h_q[1] == 0 && h_q[2] == 0 ? nullptr : kd;
+  const long n34 = (long)n3 * n4, n12 = (long)n1 * n2;
+  const int nrow34 = npair * n3;
+  cplx* out = (cplx*)outv;
+  const cplx alpha = cmk(cell_volume(a) / (double)ngl, 0);
+  FISDF_TRY(coulg_weight(c->stream, mesh, g, h_q, 1.0 / (double)ngl, 0, wt, omega));
+  if (p.b_once)
+    FISDF_TRY(pair34(c->stream, a3, a4, npair, n3, n4, n3, n4, mesh, kdp, 0, nrow34, B));
+  for (int i0 = 0; i0 < n1; i0 += p.mc) {
+    const int i1 = std::min(n1, i0 + p.mc);
+    const int R = (i1 - i0) * n2;
+    FISDF_TRY(pair_density_lr(c->stream, (const cplx*)a1v, n1, (const cplx*)a2v, n2, n2, ngrid, i0,
+                              i1, rows));
+    FISDF_TRY(fft3d(c->stream, rows, ngl, nullptr, rows, ngl, R, mesh[0], mesh[1], mesh[2], kdp, wt,
+                    nullptr));
+    FISDF_TRY(conj_inplace(c->stream, rows, (long)R * ngl));
+    FISDF_TRY(fft3d(c->stream, rows, ngl, nullptr, rows, ngl, R, mesh[0], mesh[1], mesh[2], nullptr,
+                    nullptr, nullptr));
+    for (int b0 = 0; b0 < nrow34; b0 += p.bc) {
+      const int b1 = std::min(nrow34, b0 + p.bc);
+      if (!p.b_once)
+        FISDF_TRY(pair34(c->stream, a3, a4, npair, n3, n4, n3, n4, mesh, kdp, b0, b1, B));
+      for (int pr = b0 / n3; pr <= (b1 - 1) / n3; ++pr) {
+        const int ka = std::max(b0 - pr * n3, 0), kb = std::min(b1 - pr * n3, n3);
+        FISDF_TRY(zgemm(c->stream, OP_R, OP_T, R, (kb - ka) * n4, ngrid, alpha, rows, ngl, 0,
+                        B + (long)(pr * n3 + ka - b0) * n4 * ngl, ngl, 0, ZERO,
+                        out + pr * n12 * n34 + (long)i0 * n2 * n34 + (long)ka * n4, n34, 0, 1,
+                        p.ksplit, work));
+      }
+    }
+  }
+  return 0;
+}
+
 // ---- A8 -----------------------------------------------------------------------
 static int get_k_block(fisdf_ctx* c, const void* Xv, const double* Ws_rows, long ws_Rstride,
                        const void* dmsv, int nset, int nip, int nao, const int kmesh[3],

@@ -272,4 +272,33 @@ struct KfftPlan {
 void kfft_plan(int nao, long ngrid, int nset, int rows, bool lowrank, long work_bytes,
                KfftPlan* p);
 
+// ---- exact FFT-grid four-index integrals (erifft.hip; PySCF FFTDF.get_eri / ao2mo): the exact K's
+// pair densities and transform pair, then one GEMM of the transformed rows against B ----
+constexpr int kPair34Cap = 8;          // pairs per launch of the B builder
+constexpr int kEriMaxPairs = 65535;    // npair n3 stays inside an int
+// B[(p n3 + k - r0) n4 + l][g] = exp(+i frac(g).kd) conj(a3_p[g,k]) a4_p[g,l] for the rows (p, k)
+// in [r0, r1) of the npair n3 (kd null: no phase; frac the fftfreq fractions of fft3d's phase);
+// a3, a4 host arrays of npair device pointers, (ngrid, n3) and (ngrid, n4) at leading dimensions
+// ld3, ld4.  At most kPair34Cap pairs per launch; the tile width is pair_density_variant(n4)
+int pair34(hipStream_t s, const cplx* const* a3, const cplx* const* a4, int npair, int n3, int n4,
+           long ld3, long ld4, const int mesh[3], const double* kd, int r0, int r1, cplx* B);
+// the split-K of the driver's GEMMs: the selection Gram's rule (select_gram_ksplit) with the tiles
+// of the whole n1 n2 x n3 n4 problem, so that it depends on neither the budget nor npair
+int eri_gemm_ksplit(long n12, long n34, long ngrid);
+// What fisdf_get_eri_fft does for given sizes and a byte budget W (0: kKfftWorkBytes) that holds
+// for the transform rows and for B each: mc = min(n1, W / (16 n2 ngrid)) rows i per chunk,
+// bc = min(npair n3, W / (16 n4 ngrid)) rows (p, k) per B chunk; ok = 0 when either is below 1 or
+// a size is out of range (mc = bc = bytes = 0 then).  b_once: B is one chunk, built before the row
+// loop; otherwise it is rebuilt inside each row chunk.  The arena's layout (byte offsets) and
+// total; work_elems the split-K workspace of the largest GEMM (0 at ksplit 1).
+struct EriFftPlan {
+  int ok = 0;
+  int mc = 0, nrow_chunks = 0, bc = 0, nb_chunks = 0, b_once = 0;
+  int tw = 0, ksplit = 0;
+  long work_elems = 0;
+  long off_rows = 0, off_b = 0, off_w = 0, off_work = 0, bytes = 0;
+};
+void eri_fft_plan(int n1, int n2, int n3, int n4, int npair, long ngrid, long work_bytes,
+                  EriFftPlan* p);
+
 }  // namespace fisdf

@@ -106,6 +106,13 @@ _SIGS = {
                             _i, _l, _vp], _i),
     "fisdf_kfft_lr_plan": ([_i, _l, _i, _i, _l, _ip, _ip, _ip, _ip, _ip, _ip, _ip, C.POINTER(_l),
                             C.POINTER(_l)], _i),
+    # exact FFT-grid four-index integrals
+    "fisdf_pair34": ([_vp, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _l, _l, _ip, _dp, _i, _i,
+                      _vp], _i),
+    "fisdf_get_eri_fft": ([_vp, _ip, _dp, _dp, _d, _vp, _i, _vp, _i, C.POINTER(_vp),
+                           C.POINTER(_vp), _i, _i, _i, _l, _vp], _i),
+    "fisdf_eri_fft_plan": ([_i, _i, _i, _i, _i, _l, _l, _ip, _ip, _ip, _ip, _ip, _ip, _ip,
+                            C.POINTER(_l)], _i),
     "fisdf_get_eri": ([_vp, _vp, _i, _i, _ip, _vp, C.POINTER(_vp), _ip, _vp], _i),
     "fisdf_zgemm": ([_vp, _i, _i, _i, _i, _i, _dp, _vp, _l, _l, _vp, _l, _l, _dp, _vp, _l, _l,
                      _i, _i], _i),

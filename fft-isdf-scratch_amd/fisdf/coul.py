@@ -44,25 +44,47 @@ class _Grids:
 class FFTDF:
     """The part of PySCF's ``FFTDF(cell, kpts)`` the ``get_coul`` drivers read: ``cell``,
     ``mesh`` (default ``cell.mesh``), ``grids.coords``, ``verbose``.  ``get_eri`` is the exact
-    FFT-grid ERI of PySCF, which this library does not provide: pass ``eri_ref=callable(kpts)``
-    (e.g. the test oracle's ``exact_eri``) to use the reference harness ``check_eri``."""
+    FFT-grid ERI of PySCF: with ``exact=True`` the device's own (``ISDF.eri_method = "fft"`` on
+    ``mesh``, from the ISDF object ``get_coul`` left on ``_isdf`` or else from a private one over
+    ``kpts``); or pass ``eri_ref=callable(kpts)`` (e.g. the test oracle's ``exact_eri``).  With
+    neither, ``get_eri`` raises."""
 
-    def __init__(self, cell, kpts=None, eri_ref=None):
+    def __init__(self, cell, kpts=None, eri_ref=None, exact=False):
         self.cell = cell
         self.kpts = np.zeros((1, 3)) if kpts is None else np.asarray(kpts, float).reshape(-1, 3)
         self.mesh = tuple(int(m) for m in cell.mesh)
         self.verbose = getattr(cell, "verbose", 0)
         self._eri_ref = eri_ref
+        self._exact = bool(exact)
+        self._exact_df = None     # (the ISDF object it was made from or None, the exact one)
         self._isdf = None
 
     @property
     def grids(self):
         return _Grids(self.cell, self.mesh)
 
+    def _exact_isdf(self):
+        """The object whose eri_method = "fft" integrals are this holder's exact ERIs: a copy of
+        ``_isdf`` sharing its device and resident AOs once ``get_coul`` has run, else a private
+        ``ISDF(cell, kpts)`` on ``mesh``."""
+        src = self._isdf
+        if self._exact_df is None or self._exact_df[0] is not src:
+            if src is not None:
+                import copy
+                df = copy.copy(src)
+            else:
+                df = ISDF(self.cell, self.kpts)
+                df.mesh = self.mesh
+            df.eri_method = "fft"
+            self._exact_df = (src, df)
+        return self._exact_df[1]
+
     def get_eri(self, kpts=None, compact=False):
-        if self._eri_ref is None:
-            raise NotImplementedError("exact FFTDF ERIs are PySCF's; pass eri_ref= to FFTDF")
-        return self._eri_ref(np.asarray(kpts, float).reshape(-1, 3))
+        if self._eri_ref is not None:
+            return self._eri_ref(np.asarray(kpts, float).reshape(-1, 3))
+        if self._exact:
+            return self._exact_isdf().get_eri(kpts, compact)
+        raise NotImplementedError("exact FFTDF ERIs are PySCF's; pass eri_ref= to FFTDF")
 
 
 def cutoff_to_mesh(a, ke_cutoff):
@@ -231,7 +253,9 @@ def check_eri(df_obj, kmesh, coul_q=None, x_k=None, tol=1e-4, triples=None):
 
     The ISDF ERI is evaluated on the GPU from the resident W_q / X_k of the ISDF object that
     ``get_coul`` left on ``df_obj._isdf`` (``fisdf_get_eri``); ``coul_q``/``x_k`` are accepted for
-    signature parity.  Raises ``AssertionError`` above ``tol`` (the reference's ``assert 1 == 2``
+    signature parity.  With ``FFTDF(cell, exact=True)`` both sides come from ``get_eri_many``, the
+    triples grouped by ``(k1, k2)``; the lines logged, their order and the failure are the same.
+    Raises ``AssertionError`` above ``tol`` (the reference's ``assert 1 == 2``
     at :258).  Returns the largest error seen."""
     isdf = df_obj._isdf
     if isdf is None:
@@ -244,14 +268,34 @@ def check_eri(df_obj, kmesh, coul_q=None, x_k=None, tol=1e-4, triples=None):
     kconserv2 = get_kconserv_ria(cell, vk, kmesh)
     if triples is None:
         triples = [(k1, k2, k3) for k1 in range(nk) for k2 in range(nk) for k3 in range(nk)]
+    triples = [tuple(int(k) for k in t) for t in triples]
+    errs = {}
+    if getattr(df_obj, "_exact", False) and getattr(df_obj, "_eri_ref", None) is None:
+        # the device's exact ERIs: the triples grouped by (k1, k2), whose transforms both sides
+        # pay once per group (get_eri_many)
+        exact = df_obj._exact_isdf()
+        groups = {}
+        for t in triples:
+            groups.setdefault(t[:2], []).append(t)
+        for (k1, k2), ts in groups.items():
+            ts = sorted(set(ts))
+            k34 = np.stack([vk[[k3, kconserv3[k1, k2, k3]]] for _, _, k3 in ts])
+            ref = exact.get_eri_many(vk[[k1, k2]], k34)
+            sol = isdf.get_eri_many(vk[[k1, k2]], k34)
+            for t, r, s in zip(ts, ref, sol):
+                errs[t] = abs(s - r).max()
     worst = 0.0
     for k1, k2, k3 in triples:
         q = kconserv2[k1, k2]
         k4 = kconserv3[k1, k2, k3]
         kq = vk[[k1, k2, k3, k4]]
-        eri_ref = np.asarray(df_obj.get_eri(kpts=kq, compact=False)).reshape(nao * nao, nao * nao)
-        eri_sol = isdf.get_eri(kq).reshape(nao * nao, nao * nao)
-        err = abs(eri_sol - eri_ref).max()
+        if (k1, k2, k3) in errs:
+            err = errs[(k1, k2, k3)]
+        else:
+            eri_ref = np.asarray(df_obj.get_eri(kpts=kq, compact=False)).reshape(nao * nao,
+                                                                                 nao * nao)
+            eri_sol = isdf.get_eri(kq).reshape(nao * nao, nao * nao)
+            err = abs(eri_sol - eri_ref).max()
         log.info("k1 = %2d, k2 = %2d, k3 = %2d, k4 = %2d (q = %2d) eri = %6.2e", k1, k2, k3, k4,
                  q, err)
         worst = max(worst, err)

@@ -186,6 +186,13 @@ class InterpolativeSeparableDensityFitting:
     K_FORMS = ("dm", "lowrank", "auto")
     k_rank_tol = None
     k_form_used = None
+    # where get_eri / ao2mo / get_eri_many come from: "isdf" = the fit's W_q (the reference's ERI
+    # loop, fftdf-with-k-lstsq.py:221-232); "fft" = the exact FFT-grid integrals (PySCF
+    # FFTDF.get_eri / ao2mo: the pair densities of (k1, k2) transformed forth and back with
+    # coulG(k2 - k1), then one GEMM against the pair densities of (k3, k4)) — no fitting error, no
+    # build() needed, defined at any k-points that conserve momentum.
+    eri_method = "isdf"
+    ERI_METHODS = ("isdf", "fft")
 
     def __init__(self, cell, kpts, m0=None, c0=20.0, device=None, comm=None):
         self.cell = cell
@@ -556,16 +563,11 @@ class InterpolativeSeparableDensityFitting:
             W = d.to_dev(self._wq[rep])
         return W.conj().resolve_conj() if rep != q else W
 
-    def ao2mo(self, mo_coeffs, kpts=None, compact=False):
-        """ISDF (ij|kl) for four k-points: eri[ij, kl] = sum_IJ W_q[I,J] conj(XC1)[I,i] (XC2)[I,j]
-        conj(XC3)[J,k] (XC4)[J,l], q = k2 - k1 (fftdf-with-k-lstsq.py:221-232).  Mirrors
-        FFTDF.ao2mo(mo_coeffs, kpts, compact) [pyscf]; mo_coeffs None -> AO integrals."""
+    def _eri_isdf(self, Cs, kpts, nmo):
+        """The ISDF (ij|kl) of one k-quartet, complex (n1 n2, n3 n4) on the host (fisdf_get_eri)."""
         st = self._dev_state
         assert st is not None and "Wq" in st, "call build() first"
         d = self.device
-        kpts = np.zeros((4, 3)) if kpts is None else np.asarray(kpts, float).reshape(-1, 3)
-        if kpts.shape[0] == 1:
-            kpts = np.repeat(kpts, 4, axis=0)
         kidx, v = self._kidx(kpts)
         kmesh = np.asarray(self.kmesh)
         if np.any((v[0] - v[1] + v[2] - v[3]) % kmesh):
@@ -575,13 +577,6 @@ class InterpolativeSeparableDensityFitting:
         nao = self.cell.nao_nr()
         nip = st["X"].shape[1]
         W = self._w_of_q(q).contiguous()
-        if mo_coeffs is None:
-            Cs = [None] * 4
-        elif isinstance(mo_coeffs, np.ndarray) and mo_coeffs.ndim == 2:
-            Cs = [mo_coeffs] * 4
-        else:
-            Cs = list(mo_coeffs)
-        nmo = [nao if c is None else np.asarray(c).shape[1] for c in Cs]
         dC = [None if c is None else d.to_dev(np.asarray(c, dtype=np.complex128)) for c in Cs]
         ptrs = (_lib._vp * 4)(*[None if t is None else t.data_ptr() for t in dC])
         out = d.empty((nmo[0] * nmo[1], nmo[2] * nmo[3]))
@@ -589,7 +584,39 @@ class InterpolativeSeparableDensityFitting:
         nn, np_ = _lib.iarr(nmo)
         d.ctx.call("fisdf_get_eri", _lib.ptr(st["X"]), nip, nao, kp, _lib.ptr(W), ptrs, np_,
                    _lib.ptr(out))
-        eri = out.cpu().numpy()
+        return out.cpu().numpy()
+
+    def _eri_coeffs(self, mo_coeffs):
+        """(the four coefficient matrices or None each, the four widths)."""
+        nao = self.cell.nao_nr()
+        if mo_coeffs is None:
+            Cs = [None] * 4
+        elif isinstance(mo_coeffs, np.ndarray) and mo_coeffs.ndim == 2:
+            Cs = [mo_coeffs] * 4
+        else:
+            Cs = list(mo_coeffs)
+        return Cs, [nao if c is None else np.asarray(c).shape[1] for c in Cs]
+
+    def ao2mo(self, mo_coeffs, kpts=None, compact=False, omega=None):
+        """(ij|kl) for four k-points; mirrors FFTDF.ao2mo(mo_coeffs, kpts, compact) [pyscf];
+        mo_coeffs None -> AO integrals.
+
+        eri_method = "isdf": eri[ij, kl] = sum_IJ W_q[I,J] conj(XC1)[I,i] (XC2)[I,j]
+        conj(XC3)[J,k] (XC4)[J,l], q = k2 - k1 (fftdf-with-k-lstsq.py:221-232), after build(); a
+        non-zero omega takes the W_q of _omega_df(omega).  eri_method = "fft": the exact FFT-grid
+        integrals (get_eri_many), no build() needed, at any k-points, with coulG(q, omega) (None:
+        the omega this object was fitted with)."""
+        _check_eri_method(self)
+        kpts = np.zeros((4, 3)) if kpts is None else np.asarray(kpts, float).reshape(-1, 3)
+        if kpts.shape[0] == 1:
+            kpts = np.repeat(kpts, 4, axis=0)
+        Cs, nmo = self._eri_coeffs(mo_coeffs)
+        if self.eri_method == "fft":
+            eri = self.get_eri_many(kpts[:2], kpts[None, 2:], Cs, omega)[0]
+        elif omega is not None and omega != 0:
+            return self._omega_df(float(omega)).ao2mo(mo_coeffs, kpts, compact)
+        else:
+            eri = self._eri_isdf(Cs, kpts, nmo)
         if abs(kpts).max() < 1e-9 and all(c is None or np.isrealobj(c) for c in Cs):
             eri = eri.real
             if compact and nmo[0] == nmo[1] and nmo[2] == nmo[3]:
@@ -599,9 +626,25 @@ class InterpolativeSeparableDensityFitting:
                 eri = e4[i0, i1][:, k0, k1]
         return eri
 
-    def get_eri(self, kpts=None, compact=False):
-        """AO ERIs for four k-points (FFTDF.get_eri surface [pyscf]), ISDF-factorised."""
-        return self.ao2mo(None, kpts, compact)
+    def get_eri(self, kpts=None, compact=False, omega=None):
+        """AO ERIs for four k-points (FFTDF.get_eri surface [pyscf]): ISDF-factorised, or with
+        eri_method = "fft" the exact FFT-grid ones."""
+        return self.ao2mo(None, kpts, compact, omega)
+
+    def get_eri_many(self, kpts12, kpts34, mo_coeffs=None, omega=None):
+        """(ij|kl) for one (k1, k2) and npair (k3, k4): kpts12 (2, 3), kpts34 (npair, 2, 3) ->
+        complex (npair, n1 n2, n3 n4) on the host.  eri_method = "fft": one fisdf_get_eri_fft, the
+        transforms of the (k1, k2) pair densities paid once for all pairs; "isdf": a loop of
+        fisdf_get_eri."""
+        _check_eri_method(self)
+        kpts12 = np.asarray(kpts12, float).reshape(2, 3)
+        kpts34 = np.asarray(kpts34, float).reshape(-1, 2, 3)
+        Cs, nmo = self._eri_coeffs(mo_coeffs)
+        if self.eri_method == "fft":
+            return _get_eri_fft_dev(self, kpts12, kpts34, Cs, nmo, omega)
+        if omega is not None and omega != 0:
+            return self._omega_df(float(omega)).get_eri_many(kpts12, kpts34, mo_coeffs)
+        return np.stack([self._eri_isdf(Cs, np.concatenate([kpts12, k34]), nmo) for k34 in kpts34])
 
     get_ao_eri = get_eri
 
@@ -1054,6 +1097,12 @@ def _check_k_method(df_obj):
                          f"not {df_obj.k_form!r}")
 
 
+def _check_eri_method(df_obj):
+    if df_obj.eri_method not in df_obj.ERI_METHODS:
+        raise ValueError(f"ISDF.eri_method must be one of {list(df_obj.ERI_METHODS)}, "
+                         f"not {df_obj.eri_method!r}")
+
+
 class TaggedArray(np.ndarray):
     """An ndarray that carries attributes (PySCF's tagged-array convention: a density matrix with
     the ``mo_coeff`` and ``mo_occ`` it was made from).  ``np.asarray`` of it is the plain array."""
@@ -1223,6 +1272,78 @@ def _get_k_fft_dev(df_obj, ddms, exxdiv=None, band=None, omega=None, dm=None):
         vk[:, b0:b1] = out
         del fb
     return vk
+
+
+# byte budget of the exact ERI's transform rows and of its B operand, each (fisdf_get_eri_fft
+# work_bytes); 0 = the library's default
+ERI_FFT_WORK_BYTES = 0
+
+
+def _eri_grid_aos(df_obj, kpts):
+    """The Bloch AOs on the FFT grid, device (ngrid, nao) each, at the given k-points: the resident
+    ones for points on the k-mesh, evaluated (_band_grid_aos) for any other."""
+    f = df_obj._grid_aos()
+    out, coords = [], None
+    for k in np.asarray(kpts, float).reshape(-1, 3):
+        try:
+            idx, _ = df_obj._kidx(k[None])
+            out.append(f[int(idx[0])])
+        except ValueError:
+            if coords is None:
+                coords = df_obj.grids_coords()
+            out.append(_band_grid_aos(df_obj, coords, k[None])[0].contiguous())
+    return out
+
+
+def _get_eri_fft_dev(df_obj, kpts12, kpts34, Cs, nmo, omega=None):
+    """The exact FFT-grid (ij|kl) on the device (PySCF FFTDF.get_eri / ao2mo), eri_method = "fft":
+    one fisdf_get_eri_fft for (k1, k2) and every (k3, k4) of kpts34, with coulG(k2 - k1, omega)
+    (None: the omega this object was fitted with).  The MO coefficients are applied on the device,
+    a_s = f_{k_s} C_s (fisdf_zgemm).  Host (npair, n1 n2, n3 n4)."""
+    d = df_obj.device
+    if d.sharded(df_obj):
+        raise NotImplementedError('eri_method = "fft" on a k-sharded object')
+    df_obj._kmesh()
+    cell = df_obj.cell
+    a = np.asarray(cell.lattice_vectors(), float)
+    k1, k2 = kpts12
+    for k3, k4 in kpts34:
+        s = (k1 - k2 + k3 - k4) @ a.T / (2 * np.pi)
+        if abs(s - np.rint(s)).max() > 1e-6:
+            raise ValueError("k-points violate momentum conservation k1 - k2 + k3 - k4 = G")
+    if omega is None:
+        omega = getattr(df_obj, "_fit_omega", 0.0)
+    npair = len(kpts34)
+    one = np.array([1.0, 0.0])
+    zero = np.zeros(2)
+
+    def orbitals(f, C):
+        if C is None:
+            return f
+        dC = d.to_dev(np.asarray(C, dtype=np.complex128))
+        ngrid, nao = f.shape
+        n = dC.shape[1]
+        out = d.empty((ngrid, n))
+        d.ctx.call("fisdf_zgemm", 0, 0, ngrid, n, nao, one.ctypes.data_as(_lib._dp), _lib.ptr(f),
+                   nao, 0, _lib.ptr(dC), n, 0, zero.ctypes.data_as(_lib._dp), _lib.ptr(out), n, 0,
+                   1, 1)
+        return out
+
+    f12 = _eri_grid_aos(df_obj, kpts12)
+    a1, a2 = orbitals(f12[0], Cs[0]), orbitals(f12[1], Cs[1])
+    f34 = _eri_grid_aos(df_obj, kpts34.reshape(-1, 3))
+    a3 = [orbitals(f34[2 * p], Cs[2]) for p in range(npair)]
+    a4 = [orbitals(f34[2 * p + 1], Cs[3]) for p in range(npair)]
+    p3 = (_lib._vp * npair)(*[t.data_ptr() for t in a3])
+    p4 = (_lib._vp * npair)(*[t.data_ptr() for t in a4])
+    mesh_c, mesh_p = _lib.iarr(df_obj.mesh)
+    a_c, a_p = _lib.darr(a.ravel())
+    q_c, q_p = _lib.darr(k2 - k1)
+    out = d.empty((npair, nmo[0] * nmo[1], nmo[2] * nmo[3]))
+    d.ctx.call("fisdf_get_eri_fft", mesh_p, a_p, q_p, float(omega), _lib.ptr(a1), nmo[0],
+               _lib.ptr(a2), nmo[1], p3, p4, npair, nmo[2], nmo[3], int(ERI_FFT_WORK_BYTES),
+               _lib.ptr(out))
+    return d.to_host(out)
 
 
 def _get_j_fft_dev(df_obj, ddms, band=None, omega=None):

@@ -630,6 +630,54 @@ int fisdf_kfft_lr_plan(int nao, long ngrid, int nset, int imax, long work_bytes,
                        int* h_nchunk, int* h_run_len, int* h_nrun, int* h_pair_tw, int* h_exx_sc,
                        int* h_exx_nn, long* h_row_bytes, long* h_bytes);
 
+/* ---- exact FFT-grid four-index integrals (PySCF FFTDF.get_eri / ao2mo) ---------------------------
+ * Orbitals on the FFT grid: a1 (ngrid, n1) at k1 and a2 (ngrid, n2) at k2, q = k2 - k1,
+ * em[g] = exp(-i q.r_g), and npair pairs (a3_p (ngrid, n3), a4_p (ngrid, n4)):
+ *   pair[i,j,g] = conj(a1[g,i]) a2[g,j] em[g]
+ *   v[i,j,g]    = ifft(coulG(q, omega) fft(pair[i,j,:]))[g] conj(em[g])
+ *   eri[p][i n2 + j][k n4 + l] = (vol/ngrid) sum_g v[i,j,g] conj(a3_p[g,k]) a4_p[g,l]
+ * coulG drops G = 0 at q = 0, as in the exact K.  AO integrals are a_s = f_{k_s}, MO integrals
+ * a_s = f_{k_s} C_s.  The transforms of (a1, a2) are paid once for all npair pairs (the (k3, k4)
+ * that share (k1, k2)).  With Z the transformed rows as fisdf_get_k_fft forms them,
+ * eri = (vol/ngrid) conj(Z) B^T with B[(p,k,l)][g] = conj(em[g]) conj(a3_p[g,k]) a4_p[g,l]: one
+ * GEMM with deterministic split-K, no atomics; repeated calls agree bit for bit.
+ *
+ * d_out[((p n3 + k - r0) n4 + l)][g] = conj(em[g]) conj(a3_p[g,k]) a4_p[g,l] for the rows (p, k)
+ * in [r0, r1) of the npair n3: (r1 - r0) n4 rows of ngrid.  h_d_a3, h_d_a4: host arrays of npair
+ * device pointers, (ngrid, n3) and (ngrid, n4) at leading dimensions ld3 >= n3, ld4 >= n4 (only
+ * the pairs the range meets are read).  conj(em[g]) = exp(+i frac(g).h_kd), frac the fftfreq
+ * fractions of the point's mesh indices (h_kd NULL: no phase), formed in the kernel, not stored.
+ * At most 8 pairs per launch, further launches beyond. */
+int fisdf_pair34(fisdf_ctx* ctx, const void* const* h_d_a3, const void* const* h_d_a4, int npair,
+                 int n3, int n4, long ld3, long ld4, const int mesh[3],
+                 const double* h_kd /*3 or NULL*/, int r0, int r1, void* d_out);
+/* The whole exact ERI: d_out (npair, n1 n2, n3 n4).  h_q = k2 - k1, Cartesian in 1/bohr (as
+ * h_kband of fisdf_get_k_fft); d_a1 (ngrid, n1), d_a2 (ngrid, n2) and every pair's orbitals
+ * contiguous.  omega is an argument (the context's setting is neither read nor changed).
+ * work_bytes: the byte budget that holds for the transform rows and for B each, 0 = the default
+ * (512 MiB); below one row i (n2 rows of ngrid complex) or one row (p, k) of B (n4 rows) is an
+ * error.  The result does not depend on work_bytes or on how the pairs are grouped into calls
+ * (the split-K depends on n1 n2, n3 n4 and ngrid alone).  The argument checks and the plan's
+ * verdict come before the first launch; the FFT's own checks of the mesh run when the first
+ * transform is reached, when only the arena has been written.  Either way a refused call leaves
+ * d_out untouched.  n up to 32768, npair up to 65535, ngrid < 2^31.  Workspace: the context's
+ * arena (fisdf_eri_fft_plan's bytes).  Asynchronous on the context's stream, no host
+ * synchronisation inside. */
+int fisdf_get_eri_fft(fisdf_ctx* ctx, const int mesh[3], const double a[9], const double h_q[3],
+                      double omega, const void* d_a1, int n1, const void* d_a2, int n2,
+                      const void* const* h_d_a3, const void* const* h_d_a4, int npair, int n3,
+                      int n4, long work_bytes, void* d_out /* (npair, n1 n2, n3 n4) */);
+/* what fisdf_get_eri_fft does for given sizes (host only, no context): rows i per chunk =
+ * min(n1, W / (16 n2 ngrid)) and their chunks, rows (p, k) per B chunk = min(npair n3,
+ * W / (16 n4 ngrid)) and their chunks (all four 0: the budget W is below one row of either kind),
+ * whether B is built once before the row loop (one B chunk) or again inside every row chunk, the
+ * builder's tile width (8 or 32, by n4), the GEMMs' split-K (doubled while tiles ks < 512 and
+ * ngrid / (2 ks) >= 256, tiles those of the whole n1 n2 x n3 n4 product in 64 x 64) and the arena
+ * bytes of the call.  A size out of range is an error.  Any output may be NULL */
+int fisdf_eri_fft_plan(int n1, int n2, int n3, int n4, int npair, long ngrid, long work_bytes,
+                       int* h_mc, int* h_nrow_chunks, int* h_bc, int* h_nb_chunks, int* h_b_once,
+                       int* h_tw, int* h_ksplit, long* h_bytes);
+
 /* ---- ISDF 4-index integrals (get_eri / ao2mo surface) --------------------------
  * eri[i*n2+j][k*n4+l] = sum_IJ W_q[I,J] conj(A1[I,i]) A2[I,j] conj(A3[J,k]) A4[J,l] with
  * A_s = X_{kidx[s]} C_s, q = k2 - k1 (fftdf-with-k-lstsq.py:221-232).  d_Wq: the (nip,nip)
