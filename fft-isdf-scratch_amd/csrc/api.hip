@@ -653,6 +653,14 @@ int env_fit_pipe() {
   return v;
 }
 
+int env_half_grid() {
+  static const int v = [] {
+    const char* e = getenv("FISDF_HALF_G");
+    return (e && e[0] == '0') ? 0 : 1;
+  }();
+  return v;
+}
+
 // the FFT ring's depth when fisdf_set_fit_pipe gave none: FISDF_PIPE_DEPTH, else lanes + 2
 int default_pipe_depth(int lanes) {
   static const int env = [] {
@@ -2439,14 +2447,20 @@ int fisdf_set_fit_pipe(fisdf_ctx* c, int mode, int depth) {
 }  // extern "C"
 
 namespace {
+// grow a vector of untimed events to n
+int grow_events(std::vector<hipEvent_t>& v, int n) {
+  while ((int)v.size() < n) {
+    hipEvent_t e;
+    FISDF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    v.push_back(e);
+  }
+  return 0;
+}
+
 // y of the next fit's j-th q has landed once the work enqueued so far on `st` is done
 int mark_y_ready_on(fisdf_ctx* c, int j, hipStream_t st) {
   FISDF_CHECK(j >= 0 && j < 4096, "mark_y_ready: bad index");
-  while ((int)c->ev_ready.size() <= j) {
-    hipEvent_t e;
-    FISDF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    c->ev_ready.push_back(e);
-  }
+  FISDF_TRY(grow_events(c->ev_ready, j + 1));
   if ((int)c->ready_marked.size() <= j) c->ready_marked.resize(j + 1, 0);
   FISDF_HIP(hipEventRecord(c->ev_ready[j], st));
   c->ready_marked[j] = 1;
@@ -2657,7 +2671,546 @@ static int plane_table(fisdf_ctx* c, const int mesh[3], int rows, const PlaneRef
   return 0;
 }
 
-// ---- A4 + A5 ------------------------------------------------------------------
+}  // extern "C"
+
+// ---- A4 + A5: the Coulomb fit's plan, fork, steps and driver -------
+namespace {
+
+// What one fisdf_fit_coulomb_qs call does, decided on the host before anything is enqueued: plain
+// arithmetic on what the call already knows, no HIP call.  The driver and its steps read every
+// decision from here, and fit_report_fill copies them into the record fisdf_fit_report returns.
+struct FitPlan {
+  struct Q {
+    int rank = 0, ks = 1, lane = 0;
+    int solve = -1;  // fisdf_fit_report's [6]: 0 L^-1 GEMM, 1 minimum norm, 2 blocked, -1 rank 0
+    long ncol = 0;   // grid columns fitted (the prefix planes of a half-grid q)
+    bool real = false, half = false, cod = false;
+  };
+  int nq = 0, NL = 1, D = 0;  // q, MFMA lanes, ring slots (0: the FFT runs in its lane)
+  bool pipe = false, ready = false, any_piece = false, unpack = false;
+  int rmax = 0, rfmax = 0, ncod = 0;  // largest rank, most rows transformed, minimum-norm slots
+  int ks = 1, wks = 1;                // largest HERK split (workspace), split of the W_PP GEMMs
+  bool all_full = false, lane_wpp = false;
+  std::vector<Q> q;
+};
+
+// How many lanes and ring slots the call gets, and how its y is read.
+// q are processed on NL "lanes" (the main stream and aux streams), each with its own workspaces,
+// so one q's HBM-bound FFT and memory-stalled HERK overlap another q's MFMA-bound TRSM on the
+// same CUs.
+// Pipelined FFTs (default with >= 2 lanes; fisdf_set_fit_pipe / FISDF_FIT_PIPE=0 turn it off):
+// the HBM-bound FFTs run on their own stream into a ring of D Yhat slots, ahead of the MFMA
+// lanes, which wait per q on its event — the FFTs then overlap TRSM/HERK work instead of meeting
+// another lane's FFT.  A slot is reused once the lane that read it records its `free` event, so
+// the working set is D x nip x ngrid (D = lanes + 2 by default) whatever nq is.  With a single
+// MFMA lane it is slower (C3 107.8 vs 100.9 ms/step), so one lane keeps the FFT in-lane.
+// Sharded build (fisdf_mark_y_ready): y of the call's j-th q lands at ev_ready[j] on the main
+// stream (all-to-all piece + unpack); the lanes then run on the aux streams only and each q
+// starts as soon as its own piece is there, one call for the whole shard.
+// lanes, depth: as set (depth 0: default_pipe_depth); pipe_mode 0: off
+void fit_plan_lanes(FitPlan& p, int nq, const int mesh[3], int lanes, int pipe_mode, int depth,
+                    bool ready, bool any_piece) {
+  p.nq = nq;
+  p.ready = ready;
+  p.any_piece = any_piece;
+  p.NL = std::min(nq, lanes);
+  p.pipe = pipe_mode != 0 && nq > 1 && p.NL > 1;
+  if (p.pipe) p.NL = std::min(p.NL, ready ? 2 : 3);  // aux[2] is the FFT stream
+  if (ready) p.NL = std::min(p.NL, 3);               // every lane on an aux stream
+  p.D = p.pipe ? std::min(nq, depth > 0 ? depth : default_pipe_depth(p.NL)) : 0;
+  // all-to-all pieces of a mesh whose first FFT pass cannot read plane slices in place (no
+  // register kernel, plane too large for the LDS plane kernel): each FFT-issuing stream (the FFT
+  // stream, or every lane) unpacks its q's piece into a (nip, ngrid) buffer of its own first
+  p.unpack = any_piece && !fft3d_reads_slices(mesh[0], mesh[1], mesh[2]);
+}
+
+// What follows from the ranks (known once the factorisation has been waited for): the slots
+// [s0, s0 + nq) of the factored list, their ranks, real flags and minimum-norm flags.
+void fit_plan_ranks(FitPlan& p, int nip, const int mesh[3], const int kmesh[3], const int* h_qs,
+                    int s0, const std::vector<int>& f_rank, const std::vector<char>& f_real,
+                    const std::vector<char>& f_cod, bool half_on, int ncu) {
+  const long ngrid = (long)mesh[0] * mesh[1] * mesh[2];
+  p.q.assign(p.nq, FitPlan::Q{});
+  p.rmax = p.ncod = 0;
+  p.ks = 1;
+  p.all_full = true;
+  for (int lq = 0; lq < p.nq; ++lq) {
+    FitPlan::Q& pq = p.q[lq];
+    const int sl = s0 + lq, r = f_rank[sl];
+    pq.rank = r;
+    pq.lane = lq % p.NL;
+    pq.real = f_real[sl] != 0;
+    // a self-conjugate q is fitted on the prefix planes of its Hermitian G pairs (about half the
+    // grid): Re W = sum over one member of each pair with the pair's combined weight
+    pq.half = half_on && pq.real;
+    pq.ncol = ngrid;
+    if (pq.half) {
+      int m[3];
+      self_conjugate_m(kmesh, h_qs[lq], m);
+      pq.ncol = (long)half_prefix_planes(mesh[0], m[0]) * mesh[1] * mesh[2];
+    }
+    // minimum-norm slots transform all nip rows of y (the operator A^+ mixes every row)
+    pq.cod = sl < (int)f_cod.size() && f_cod[sl] != 0;
+    pq.solve = r == 0 ? -1 : pq.cod ? 1 : r == nip ? 0 : 2;
+    // split-K of each q's HERK from its own rank (not the call's largest), so a q's arithmetic
+    // does not depend on which other q share the call (1-GPU vs sharded builds agree bitwise);
+    // the workspace holds the largest split over the whole grid
+    pq.ks = pick_ksplit_herk(r, (int)pq.ncol, ncu);
+    p.ks = std::max(p.ks, pick_ksplit_herk(r, (int)ngrid, ncu));
+    p.rmax = std::max(p.rmax, r);
+    p.ncod += pq.cod ? 1 : 0;
+    p.all_full = p.all_full && r == nip;
+  }
+  p.rfmax = p.ncod ? nip : p.rmax;
+  // every q full rank (the production regime) and many q in the call: each q's W_PP =
+  // L^-H G L^-1 and its scatter run in its lane right after its HERK, overlapped with the other
+  // q's fit, instead of as a batched tail after the lanes join (the same kernel per output, batch
+  // 1: W_q unchanged bit for bit).  C3 on one GPU (36 q): 79.89 vs 80.21 ms/step; a k-shard's 4-5
+  // q: +0.6 ms per rank (the last q of each lane then waits for its own small GEMMs), so below
+  // kLaneWppMinQ q the batched tail stays.  FISDF_LANE_WPP: 0 never, 1 always
+  p.lane_wpp = lane_wpp_wanted(p.nq) && p.all_full && p.ncod == 0;
+  // W_PP = L^-H G L^-1 (two upper-triangular nip^3 GEMMs per q) split over K: 100 output tiles
+  // of 64 x 64 at C3 leave most CUs idle for ~180 us per GEMM, in every lane, for every q.  The
+  // split depends on nip only, the same in the lanes and in the batched tail (W_q bitwise equal
+  // between the 1-GPU and the k-sharded builds).  FISDF_WPP_KSPLIT (read per call; 1 = off)
+  p.wks = wpp_ksplit(nip);
+}
+
+// the arena of one call, carved in this order
+struct FitLayout {
+  size_t oY[4] = {0, 0, 0, 0}, oU[4] = {0, 0, 0, 0}, oK[4] = {0, 0, 0, 0}, oTc[4] = {0, 0, 0, 0};
+  size_t oP[4] = {0, 0, 0, 0};                            // unpack buffers (FFT stream 0, lane l -> l)
+  size_t oWk = 0, oG = 0, oT = 0, oS = 0, oMS = 0, oMT = 0, total = 0;
+};
+
+FitLayout fit_layout(const FitPlan& p, int nip, long ngrid) {
+  const long rr = (long)p.rmax * p.rmax, nn = (long)nip * nip;
+  FitLayout o;
+  Carver cv;
+  for (int l = 0; l < p.NL; ++l) {
+    if (!p.pipe) o.oY[l] = cv.take(sizeof(cplx) * p.rfmax * ngrid);
+    o.oU[l] = cv.take(sizeof(cplx) * p.rmax * ngrid);
+    o.oK[l] = cv.take(sizeof(cplx) * (size_t)p.ks * p.rmax * p.rmax);
+    o.oTc[l] = cv.take(sizeof(cplx) * rr);
+  }
+  if (p.unpack)
+    for (int l = 0; l < (p.pipe ? 1 : p.NL); ++l) o.oP[l] = cv.take(sizeof(cplx) * (size_t)nip * ngrid);
+  if (p.wks > 1) o.oWk = cv.take(sizeof(cplx) * (size_t)p.NL * p.wks * rr);
+  o.oG = cv.take(sizeof(cplx) * p.nq * rr);  // (nq, rmax, rmax): G_q in the leading r_q x r_q block
+  o.oT = cv.take(sizeof(cplx) * p.nq * rr);
+  o.oS = cv.take(sizeof(cplx) * p.nq * rr);
+  if (p.ncod) {
+    o.oMS = cv.take(sizeof(cplx) * (size_t)p.ncod * p.rmax * nip);  // G M per min-norm slot
+    o.oMT = cv.take(sizeof(cplx) * nn);                              // M^H G M
+  }
+  o.total = cv.off;
+  return o;
+}
+
+const cplx* fit_piece(const fisdf_ctx* c, int lq) {
+  return lq < (int)c->y_piece.size() ? c->y_piece[lq] : nullptr;
+}
+
+// the record fisdf_fit_report reads (what the plan decides; the FFT form [3] and the asymmetric
+// count [5] are filled in where they are found)
+void fit_report_fill(fisdf_ctx* c, const FitPlan& p) {
+  c->fit_report.assign(p.nq, fisdf_ctx::FitRec{});
+  for (int lq = 0; lq < p.nq; ++lq) {
+    const FitPlan::Q& pq = p.q[lq];
+    int* v = c->fit_report[lq].v;
+    v[0] = pq.rank;
+    v[1] = pq.real ? 1 : 0;
+    v[2] = pq.half ? 1 : 0;
+    v[4] = (int)pq.ncol;
+    v[6] = pq.solve;
+    v[7] = pq.cod ? 1 : 0;
+    v[8] = pq.lane;
+    v[9] = p.lane_wpp ? 1 : p.all_full ? 0 : 2;
+    v[10] = (p.lane_wpp || p.all_full) ? p.wks : 1;
+    v[11] = fit_piece(c, lq) ? (p.unpack ? 2 : 1) : 0;
+  }
+}
+
+// The ring outside the arena (nip rows per slot, whatever the ranks turn out to be) and the events
+// of the pipelined mode; without the memory for the ring, the in-lane FFT.
+int fit_ring(fisdf_ctx* c, FitPlan& p, int nip, long ngrid) {
+  if (!p.pipe) return 0;
+  const size_t rb = sizeof(cplx) * (size_t)p.D * nip * ngrid;
+  if (rb > c->f_ring_bytes) {
+    if (c->f_ring) FISDF_HIP(hipFree(c->f_ring));
+    c->f_ring = nullptr;
+    c->f_ring_bytes = 0;
+    if (hipMalloc(&c->f_ring, rb) == hipSuccess) {
+      c->f_ring_bytes = rb;
+    } else {
+      // only pipe and D are cleared: NL keeps the cap (2 ready, else 3) it got while pipe was
+      // still true, so such a call runs fewer lanes than one that asked for no pipe
+      (void)hipGetLastError();
+      c->f_ring = nullptr;
+      p.pipe = false;
+      p.D = 0;
+      return 0;
+    }
+  }
+  FISDF_TRY(grow_events(c->ev_q, p.nq));
+  return grow_events(c->ev_free, p.D);
+}
+
+// one call's state, shared by its steps
+struct FitCall {
+  fisdf_ctx* c = nullptr;
+  FitPlan p;
+  FitLayout o;
+  // the arguments
+  const int* h_qs = nullptr;
+  int nip = 0;
+  const int *mesh = nullptr, *kmesh = nullptr;
+  const double* a = nullptr;
+  const cplx* yT = nullptr;
+  cplx* Wq = nullptr;
+  int s0 = 0, nb = 0;                 // first factor slot, block of the blocked substitution
+  long ngrid = 0, nn = 0, rr = 0, sLi = 0;
+  char* b = nullptr;                  // the arena
+  cplx *G = nullptr, *T = nullptr, *S = nullptr;
+  hipStream_t lane_st[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipStream_t fst = nullptr;          // the FFT stream of the pipelined mode
+  bool aux_used[3] = {false, false, false};
+  const PlaneRef* planes = nullptr;
+  CellGeom g;
+  double wscale = 0;  // sqrt(coulG(k_q+G) vol/N^2)  (:114-115 and the Parseval 1/N of :118)
+};
+
+// Which stream lane l runs on: aux[ready ? l : l - 1], lane 0 of a call that is not ready on the
+// context's stream; the FFT stream of the pipelined mode is aux[2].  A ready call's lanes first
+// wait for ev_ready[0]: everything enqueued before the first piece landed (the y build, the
+// arena's previous users) is complete there.  G is zeroed on lane 0 and the other streams start
+// behind that (ev_fork).  A one-lane, in-lane-FFT call that is not ready touches no aux stream.
+int fit_fork(FitCall& f) {
+  fisdf_ctx* c = f.c;
+  const FitPlan& p = f.p;
+  const bool forked = p.ready || p.NL > 1 || p.pipe;
+  if (forked) FISDF_TRY(ensure_aux(c));
+  f.lane_st[0] = c->stream;
+  for (int l = p.ready ? 0 : 1; l < p.NL; ++l) {
+    const int i = p.ready ? l : l - 1;
+    f.lane_st[l] = c->aux[i];
+    f.aux_used[i] = true;
+    aux_fork(c, i);
+    if (p.ready) FISDF_HIP(hipStreamWaitEvent(f.lane_st[l], c->ev_ready[0], 0));
+  }
+  FISDF_HIP(hipMemsetAsync(f.G, 0, sizeof(cplx) * p.nq * f.rr, f.lane_st[0]));
+  if (!forked) return 0;
+  FISDF_HIP(hipEventRecord(c->ev_fork, f.lane_st[0]));
+  for (int l = 1; l < p.NL; ++l) FISDF_HIP(hipStreamWaitEvent(f.lane_st[l], c->ev_fork, 0));
+  if (p.pipe) {
+    f.fst = c->aux[2];
+    f.aux_used[2] = true;
+    aux_fork(c, 2);
+    FISDF_HIP(hipStreamWaitEvent(f.fst, c->ev_fork, 0));
+  }
+  return 0;
+}
+
+// join the lanes (and the FFT stream: that keeps the arena reuse ordered) before the batched
+// small stage on the main stream
+// (this join is what makes fisdf_build's build_return(c, yT) right after this call safe: every
+// FFT / lane read of y is ordered before the caller's stream-ordered free on c->stream)
+int fit_join(FitCall& f) {
+  for (int i = 0; i < 3; ++i)
+    if (f.aux_used[i]) FISDF_TRY(aux_join(f.c, i));
+  return join_factors(f.c);
+}
+
+// the weights of q lq, cached per q
+int fit_weight(FitCall& f, hipStream_t st, int lq, const double** w) {
+  return get_weight(f.c, st, f.mesh, f.kmesh, f.a, f.h_qs[lq], f.wscale, f.p.q[lq].half, w);
+}
+
+cplx* fit_slot(const FitCall& f, int lq) {
+  return f.c->f_ring + (long)(lq % f.p.D) * f.nip * f.ngrid;
+}
+
+// Yhat_q = FFT(y_q[:, piv] * f_q) * w_q   (:99, :113-115, :118; rows in pivot order); the
+// sharded build reads q in place from their all-to-all pieces (fisdf_set_y_slices) through a
+// per-plane address table (plane-aligned slices)
+// ub: the stream's unpack buffer (FFT stream 0, lane l -> l)
+int fit_fft(FitCall& f, hipStream_t st, int lq, cplx* Yh, int ub) {
+  fisdf_ctx* c = f.c;
+  const FitPlan::Q& pq = f.p.q[lq];
+  const int* mesh = f.mesh;
+  const int nip = f.nip, sl = f.s0 + lq;
+  const long ngrid = f.ngrid;
+  const int r = pq.cod ? nip : pq.rank;
+  double kq[3], kd[3];
+  kpoint(f.kmesh, f.g, f.h_qs[lq], kq);
+  for (int i = 0; i < 3; ++i) kd[i] = f.g.a[i][0] * kq[0] + f.g.a[i][1] * kq[1] + f.g.a[i][2] * kq[2];
+  const double* wt = nullptr;
+  FISDF_TRY(fit_weight(f, st, lq, &wt));
+  // a half-grid q: its transform pairs G with -G - m (m = 2 k_q, the phase exp(-i k_q.r) times
+  // a real input), so the FFT writes the prefix planes only and moves half of its intermediate
+  // (fft3d herm); m from the phase actually applied must match the pairing the weights use
+  int herm_m[3];
+  bool herm = pq.half;
+  if (herm) {
+    int m[3];
+    self_conjugate_m(f.kmesh, f.h_qs[lq], m);
+    for (int d = 0; d < 3; ++d) {
+      const double t = kd[d] / M_PI;
+      const long tm2 = std::lround(t);
+      herm = herm && std::fabs(t - (double)tm2) < 1e-9 &&
+             ((tm2 % mesh[d]) + mesh[d]) % mesh[d] == m[d] % mesh[d];
+      herm_m[d] = m[d];
+    }
+  }
+  const int* hm = herm ? herm_m : nullptr;
+  c->fit_report[lq].v[3] = fft3d_route(mesh[0], mesh[1], mesh[2], hm) == FFT_REG_HERM ? 1 : 0;
+  // y of this q stored real by the composite build's y kernel (fisdf_build_y_qs)
+  const bool y_real = f.yT != nullptr && lq < (int)c->y_real_slot.size() && c->y_real_slot[lq];
+  StageTimer tm(c, FISDF_ST_FFT, st);
+  const cplx* pc = fit_piece(c, lq);
+  FISDF_CHECK(pc || f.yT, "fit_coulomb: q without y");
+#ifdef FISDF_EXP_NOFFT  // timing experiment only (wrong results)
+  return 0;
+#endif
+  if (pc && f.p.unpack) {  // piece -> (nip, ngrid) rows, stream-ordered before the FFT reads them
+    cplx* yb = (cplx*)(f.b + f.o.oP[ub]);
+    const char* src = (const char*)pc;
+    for (size_t p = 0; p + 1 < c->y_slices.size(); p += 2) {
+      const long g0 = c->y_slices[p], ng = c->y_slices[p + 1];
+      FISDF_CHECK(g0 + ng <= ngrid, "fit_coulomb: y slice out of the mesh");
+      if (ng == 0) continue;
+      FISDF_HIP(hipMemcpy2DAsync(yb + g0, sizeof(cplx) * ngrid, src, sizeof(cplx) * ng,
+                                 sizeof(cplx) * ng, nip, hipMemcpyDeviceToDevice, st));
+      src += sizeof(cplx) * (size_t)ng * nip;
+    }
+    FISDF_TRY(fft3d(st, yb, ngrid, c->f_piv + (long)sl * nip, Yh, ngrid, r, mesh[0], mesh[1],
+                    mesh[2], kd, wt, nullptr, nullptr, hm));
+    return 0;
+  }
+  FISDF_CHECK(!(pc && y_real), "fit_coulomb: a real y slot with a y piece");
+  FISDF_TRY(fft3d(st, pc ? pc : f.yT + (long)lq * nip * ngrid, ngrid, c->f_piv + (long)sl * nip, Yh,
+                  ngrid, r, mesh[0], mesh[1], mesh[2], kd, wt, nullptr, pc ? f.planes : nullptr,
+                  hm, y_real));
+  return 0;
+}
+
+// FFT of q lq into its ring slot, after the lane that read the slot's previous q is done
+int fit_enqueue_fft(FitCall& f, int lq) {
+  fisdf_ctx* c = f.c;
+  const FitPlan& p = f.p;
+  if (lq >= p.nq || p.q[lq].rank == 0) return 0;
+  if (lq >= p.D) FISDF_HIP(hipStreamWaitEvent(f.fst, c->ev_free[lq % p.D], 0));
+  if (p.ready) FISDF_HIP(hipStreamWaitEvent(f.fst, c->ev_ready[lq], 0));
+  FISDF_TRY(fit_fft(f, f.fst, lq, fit_slot(f, lq), 0));
+  FISDF_HIP(hipEventRecord(c->ev_q[lq], f.fst));
+  return 0;
+}
+
+// U = L^{-1} Yh   (fit, factored order; (x4_q)_PP = L L^H): one GEMM (timed kernel-exact) on a
+// full-rank q and on a minimum-norm q; the basic solution of a rank-deficient q
+// (FISDF_FIT_BASIC) substitutes block by block
+int fit_solve(FitCall& f, int lq, cplx* Yh, cplx* U) {
+  fisdf_ctx* c = f.c;
+  const FitPlan::Q& pq = f.p.q[lq];
+  hipStream_t st = f.lane_st[pq.lane];
+  const int nip = f.nip, sl = f.s0 + lq, r = pq.rank, ncol = (int)pq.ncol;
+  const long ngrid = f.ngrid, nn = f.nn;
+  const bool real_q = pq.real;
+  StageTimer tm(c, FISDF_ST_TRSM, st, pq.solve != 2);
+  if (pq.solve == 1) {  // U = A^+ Yh[P]: the minimum-norm operator over all nip rows
+    FISDF_TRY(zgemm(st, OP_N, OP_N, r, ncol, nip, ONE, c->f_M + (long)sl * nn, nip, 0, Yh, ngrid, 0,
+                    ZERO, U, ngrid, 0, 1, 1, nullptr, EPI_NONE, nullptr,
+                    real_q ? GEMM_A_REAL : GEMM_FULL));
+  } else if (pq.solve == 0) {  // one lower-triangular GEMM with L^{-1}
+#ifdef FISDF_EXP_NOREALTRSM  // timing experiment only (wrong results)
+    if (real_q) return 0;
+#endif
+    FISDF_TRY(zgemm(st, OP_N, OP_N, nip, ncol, nip, ONE, c->f_Li + (long)sl * nn, nip, 0, Yh, ngrid,
+                    0, ZERO, U, ngrid, 0, 1, 1, nullptr, EPI_NONE, nullptr,
+                    GEMM_A_LOWER | (real_q ? GEMM_A_REAL : GEMM_FULL)));
+  } else {
+    FISDF_TRY(trsm_blocked(st, 1, c->f_Lp + (long)sl * nn, nip, 0, r, c->f_Linv + (long)sl * f.sLi,
+                           0, f.nb, Yh, ngrid, 0, U, ngrid, 0, ncol, 1, real_q ? 1 : 0));
+  }
+  return 0;
+}
+
+// G = U U^H  (:121 by Parseval); of a real-factor q the HERK forms Re G only, and Im G comes from
+// the weight-asymmetric G alone: every other (G, G') pair cancels.  scratch: r x ngrid (Yhat of
+// this q, no longer needed)
+int fit_gram(FitCall& f, int lq, const cplx* U, cplx* scratch) {
+  fisdf_ctx* c = f.c;
+  const FitPlan::Q& pq = f.p.q[lq];
+  hipStream_t st = f.lane_st[pq.lane];
+  const int r = pq.rank, ncol = (int)pq.ncol, rmax = f.p.rmax, q = f.h_qs[lq];
+  const long ngrid = f.ngrid;
+  cplx* kw = (cplx*)(f.b + f.o.oK[pq.lane]);
+  cplx* Tc = (cplx*)(f.b + f.o.oTc[pq.lane]);
+  cplx* Gq = f.G + lq * f.rr;
+  {
+    StageTimer tm(c, FISDF_ST_HERK, st, true);
+    FISDF_TRY(herk(st, r, ncol, 1.0, U, ngrid, Gq, rmax, pq.ks, kw,
+                   pq.real ? GEMM_RE_ONLY : GEMM_FULL));
+  }
+  if (!pq.real) return 0;
+  StageTimer tm(c, FISDF_ST_SMALL, st);
+  const fisdf_ctx::Asym* as = nullptr;
+  if (pq.half) {
+    // half grid: one member of each asymmetric pair, Im W = Im(U_A diag(f) U_A^H)
+    FISDF_TRY(get_asym_half(c, st, f.mesh, f.kmesh, f.a, q, f.wscale, &as));
+    c->fit_report[lq].v[5] = as->n;
+    // scratch holds r x ngrid: the plain and the scaled copy of at most ngrid / 2 listed
+    // columns at a time (one pass unless more than half the grid is listed, which takes a
+    // mesh whose planes are all self-paired, n0 <= 2)
+    const int cap = (int)std::max(1L, ngrid / 2);
+    for (int o = 0; o < as->n; o += cap) {
+      const int na = std::min(cap, as->n - o);
+      cplx* plain = scratch;
+      cplx* scaled = scratch + (long)r * na;
+      FISDF_TRY(gather_cols_scaled(st, U, ngrid, r, as->idx + o, nullptr, na, plain));
+      FISDF_TRY(gather_cols_scaled(st, U, ngrid, r, as->idx + o, as->f + o, na, scaled));
+      FISDF_TRY(zgemm(st, OP_N, OP_C, r, r, na, ONE, scaled, na, 0, plain, na, 0, ZERO, Tc, rmax, 0,
+                      1, std::min(pq.ks, std::max(1, na / 256)), kw));
+      FISDF_TRY(add_imag(st, Gq, rmax, Tc, rmax, r));
+    }
+  } else {
+    const double* wt = nullptr;
+    FISDF_TRY(fit_weight(f, st, lq, &wt));
+    FISDF_TRY(get_asym(c, st, f.mesh, f.kmesh, f.a, q, wt, &as));
+    c->fit_report[lq].v[5] = as->n;
+    if (as->n > 0) {
+      FISDF_TRY(gather_cols(st, U, ngrid, r, as->idx, as->n, scratch));
+      FISDF_TRY(herk(st, r, as->n, 1.0, scratch, as->n, Tc, rmax,
+                     std::min(pq.ks, std::max(1, as->n / 256)), kw));
+      FISDF_TRY(add_imag(st, Gq, rmax, Tc, rmax, r));
+    }
+  }
+  return 0;
+}
+
+// W_PP = L^-H G L^-1 of this q in its lane (S = L^-H G, W_PP = L^-H S^H), scattered
+int fit_wpp_lane(FitCall& f, int lq) {
+  fisdf_ctx* c = f.c;
+  const FitPlan& p = f.p;
+  const int nip = f.nip, sl = f.s0 + lq, ln = p.q[lq].lane, rmax = p.rmax, wks = p.wks;
+  const long rr = f.rr;
+  hipStream_t st = f.lane_st[ln];
+  StageTimer tm(c, FISDF_ST_SMALL, st);
+  const cplx* Lf = c->f_Li + (long)sl * f.nn;
+  cplx* wk = wks > 1 ? (cplx*)(f.b + f.o.oWk) + (long)ln * wks * rr : nullptr;
+  FISDF_TRY(zgemm(st, OP_C, OP_N, nip, nip, nip, ONE, Lf, nip, 0, f.G + lq * rr, rmax, 0, ZERO,
+                  f.S + lq * rr, rmax, 0, 1, wks, wk, EPI_NONE, nullptr, GEMM_A_UPPER));
+  FISDF_TRY(zgemm(st, OP_C, OP_C, nip, nip, nip, ONE, Lf, nip, 0, f.S + lq * rr, rmax, 0, ZERO,
+                  f.T + lq * rr, rmax, 0, 1, wks, wk, EPI_NONE, nullptr, GEMM_A_UPPER));
+  FISDF_TRY(scatter_w(st, f.T + lq * rr, rmax, rr, rmax, c->f_piv + (long)sl * nip,
+                      c->f_rank_dev + sl, f.Wq + lq * f.nn, nip, 1));
+  return 0;
+}
+
+// What one q enqueues on its lane, in order: the wait for its Yhat (its ring slot's event, or its
+// own ready mark and the FFT in the lane), the wait for its factor, the solve, the Gram, the
+// ring slot handed back with the FFT D q ahead enqueued, and W_PP when it runs in the lane.
+int fit_q(FitCall& f, int lq) {
+  fisdf_ctx* c = f.c;
+  const FitPlan& p = f.p;
+  const FitPlan::Q& pq = p.q[lq];
+  if (pq.rank == 0) return p.pipe ? fit_enqueue_fft(f, lq + p.D) : 0;
+  const int sl = f.s0 + lq;  // factor slot
+  hipStream_t st = f.lane_st[pq.lane];
+  cplx* Yh = p.pipe ? fit_slot(f, lq) : (cplx*)(f.b + f.o.oY[pq.lane]);
+  cplx* U = (cplx*)(f.b + f.o.oU[pq.lane]);  // where L^{-1} Yh lands
+  if (p.pipe) {
+    FISDF_HIP(hipStreamWaitEvent(st, c->ev_q[lq], 0));
+  } else {
+    if (p.ready) FISDF_HIP(hipStreamWaitEvent(st, c->ev_ready[lq], 0));
+    FISDF_TRY(fit_fft(f, st, lq, Yh, pq.lane));
+  }
+  // L^-1, Q, ...: the slots built first need only their own (ev_fac_early); a lane's later q
+  // wait for all of them
+  if (c->f_fac_unjoined)
+    FISDF_HIP(hipStreamWaitEvent(st, (sl < c->f_early && !pq.cod) ? c->ev_fac_early : c->ev_fac, 0));
+  FISDF_TRY(fit_solve(f, lq, Yh, U));
+  FISDF_TRY(fit_gram(f, lq, U, Yh));
+  if (p.pipe) {  // this lane is done with the ring slot: the FFT D q ahead may overwrite it
+    FISDF_HIP(hipEventRecord(c->ev_free[lq % p.D], st));
+    FISDF_TRY(fit_enqueue_fft(f, lq + p.D));
+  }
+  if (p.lane_wpp) FISDF_TRY(fit_wpp_lane(f, lq));
+  return 0;
+}
+
+// W_PP = L^{-H} G L^{-1} for all q of the shard at once on the main stream (L padded with
+// identity, G with zeros beyond each rank):  T = L^{-H} G ; S = L^{-H} T^H ; W_PP = S^H ; scatter
+// by pivots
+int fit_tail(FitCall& f) {
+  fisdf_ctx* c = f.c;
+  const FitPlan& p = f.p;
+  const int nip = f.nip, nq = p.nq, s0 = f.s0, rmax = p.rmax, NL = p.NL, wks = p.wks, nb = f.nb;
+  const long nn = f.nn, rr = f.rr, sLi = f.sLi;
+  cplx *G = f.G, *T = f.T, *S = f.S;
+  StageTimer tm(c, FISDF_ST_SMALL);
+  const cplx* Lp0 = c->f_Lp + (long)s0 * nn;
+  const cplx* Li0 = c->f_Linv + (long)s0 * sLi;
+  // minimum-norm slots: G M first (the batched back-substitutions below overwrite G)
+  for (int lq = 0, j = 0; lq < nq && p.ncod; ++lq) {
+    const int sl = s0 + lq, r = p.q[lq].rank;
+    if (!p.q[lq].cod) continue;
+    FISDF_TRY(zgemm(c->stream, OP_N, OP_N, r, nip, r, ONE, G + lq * rr, rmax, 0,
+                    c->f_M + (long)sl * nn, nip, 0, ZERO, (cplx*)(f.b + f.o.oMS) + (long)j++ * rmax * nip,
+                    nip, 0, 1));
+  }
+  if (p.all_full) {
+    // with L^{-1} at hand, two batched GEMMs whose A = L^{-H} is upper triangular (each
+    // M-tile starts its K loop at its own row: half the flops of dense GEMMs):
+    //   S = L^{-H} G,  W_PP = L^{-H} S^H  (= L^{-H} G L^{-1}, G Hermitian)
+    const cplx* Lf = c->f_Li + (long)s0 * nn;
+    if (wks > 1) {
+      // the lanes' split workspace, NL q at a time (per-q arithmetic as in the lanes)
+      cplx* wk = (cplx*)(f.b + f.o.oWk);
+      for (int z0 = 0; z0 < nq; z0 += NL) {
+        const int nz = std::min(NL, nq - z0);
+        FISDF_TRY(zgemm(c->stream, OP_C, OP_N, nip, nip, nip, ONE, Lf + (long)z0 * nn, nip, nn,
+                        G + z0 * rr, rmax, rr, ZERO, S + z0 * rr, rmax, rr, nz, wks, wk, EPI_NONE,
+                        nullptr, GEMM_A_UPPER));
+        FISDF_TRY(zgemm(c->stream, OP_C, OP_C, nip, nip, nip, ONE, Lf + (long)z0 * nn, nip, nn,
+                        S + z0 * rr, rmax, rr, ZERO, T + z0 * rr, rmax, rr, nz, wks, wk, EPI_NONE,
+                        nullptr, GEMM_A_UPPER));
+      }
+    } else {
+      FISDF_TRY(zgemm(c->stream, OP_C, OP_N, nip, nip, nip, ONE, Lf, nip, nn, G, rmax, rr, ZERO,
+                      S, rmax, rr, nq, 1, nullptr, EPI_NONE, nullptr, GEMM_A_UPPER));
+      FISDF_TRY(zgemm(c->stream, OP_C, OP_C, nip, nip, nip, ONE, Lf, nip, nn, S, rmax, rr, ZERO,
+                      T, rmax, rr, nq, 1, nullptr, EPI_NONE, nullptr, GEMM_A_UPPER));
+    }
+  } else {
+    FISDF_TRY(trsm_blocked(c->stream, 0, Lp0, nip, nn, rmax, Li0, sLi, nb, G, rmax, rr,
+                           T, rmax, rr, rmax, nq));
+    FISDF_TRY(conj_transpose(c->stream, T, rmax, rr, G, nq));
+    FISDF_TRY(trsm_blocked(c->stream, 0, Lp0, nip, nn, rmax, Li0, sLi, nb, G, rmax, rr,
+                           S, rmax, rr, rmax, nq));
+    FISDF_TRY(conj_transpose(c->stream, S, rmax, rr, T, nq));
+  }
+  FISDF_TRY(scatter_w(c->stream, T, rmax, rr, rmax, c->f_piv + (long)s0 * nip,
+                      c->f_rank_dev + s0, f.Wq, nip, nq));
+  // minimum-norm slots: W_PP = M^H (G M) (nip x nip: z[P] = M^H U) replaces the above
+  for (int lq = 0, j = 0; lq < nq && p.ncod; ++lq) {
+    const int sl = s0 + lq, r = p.q[lq].rank;
+    if (!p.q[lq].cod) continue;
+    const cplx* MS = (cplx*)(f.b + f.o.oMS) + (long)j++ * rmax * nip;
+    cplx* MT = (cplx*)(f.b + f.o.oMT);
+    const cplx* Mq = c->f_M + (long)sl * nn;
+    FISDF_TRY(zgemm(c->stream, OP_C, OP_N, nip, nip, r, ONE, Mq, nip, 0, MS, nip, 0, ZERO, MT,
+                    nip, 0, 1));
+    FISDF_TRY(scatter_w(c->stream, MT, nip, 0, nip, c->f_piv + (long)sl * nip, c->f_nip_dev,
+                        f.Wq + lq * nn, nip, 1));
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
 int fisdf_fit_coulomb_qs(fisdf_ctx* c, const int* h_qs, int nq, const void* yTv, int nip,
                          const int mesh[3], const int kmesh[3], const double a[9], void* Wqv) {
   FISDF_TRY(device_guard(c));
@@ -2679,482 +3232,62 @@ int fisdf_fit_coulomb_qs(fisdf_ctx* c, const int* h_qs, int nq, const void* yTv,
   FISDF_CHECK(it0 != c->f_qs.end() && (it0 - c->f_qs.begin()) + nq <= (long)c->f_qs.size() &&
                   std::equal(h_qs, h_qs + nq, it0),
               "fit_coulomb: the q-list must be a contiguous run of the factored q-list");
-  const int s0 = (int)(it0 - c->f_qs.begin());
-  auto piece_of = [&](int lq) -> const cplx* {
-    return lq < (int)c->y_piece.size() ? c->y_piece[lq] : nullptr;
-  };
-  const long ngrid = (long)mesh[0] * mesh[1] * mesh[2];
-  const long nn = (long)nip * nip;
-  const int nb = c->f_nb;
-  const int nblk = (nip + nb - 1) / nb;
-  CellGeom g;
-  lattice(a, g);
-  const double vol = cell_volume(a);
-  const cplx* yT = (const cplx*)yTv;
-  cplx* Wq = (cplx*)Wqv;
-  // q are processed on NL "lanes" (the main stream and aux streams), each with its own
-  // workspaces, so one q's HBM-bound FFT and memory-stalled HERK overlap another q's
-  // MFMA-bound TRSM on the same CUs
-  int NL = std::min(nq, c->lanes > 0 ? c->lanes : env_fit_lanes());
-  // Pipelined FFTs (default with >= 2 lanes; fisdf_set_fit_pipe / FISDF_FIT_PIPE=0 turn it
-  // off): the HBM-bound FFTs run on their own stream into a ring of D Yhat slots, ahead of the
-  // MFMA lanes, which wait per q on its event — the FFTs then overlap TRSM/HERK work instead of
-  // meeting another lane's FFT.  A slot is reused once the lane that read it records its
-  // `free` event, so the working set is D x nip x ngrid (D = lanes + 2 by default) whatever
-  // nq is.  With a single MFMA lane it is slower (C3 107.8 vs 100.9 ms/step), so one lane
-  // keeps the FFT in-lane.
-  const int pipe_mode = c->pipe_mode >= 0 ? c->pipe_mode : env_fit_pipe();
-  bool pipe = pipe_mode != 0 && nq > 1 && NL > 1;
-  // sharded build (fisdf_mark_y_ready): y of the call's j-th q lands at ev_ready[j] on the main
-  // stream (all-to-all piece + unpack); the lanes then run on the aux streams only and each q
-  // starts as soon as its own piece is there, one call for the whole shard
+  FitCall f;
+  FitPlan& p = f.p;
+  f.c = c;
+  f.h_qs = h_qs;
+  f.nip = nip;
+  f.mesh = mesh;
+  f.kmesh = kmesh;
+  f.a = a;
+  f.yT = (const cplx*)yTv;
+  f.Wq = (cplx*)Wqv;
+  f.s0 = (int)(it0 - c->f_qs.begin());
+  f.nb = c->f_nb;
+  f.ngrid = (long)mesh[0] * mesh[1] * mesh[2];
+  f.nn = (long)nip * nip;
+  f.sLi = (long)((nip + f.nb - 1) / f.nb) * f.nb * f.nb;
+  lattice(a, f.g);
+  f.wscale = cell_volume(a) / ((double)f.ngrid * f.ngrid);
   int nready = 0;
-  for (int lq = 0; lq < nq; ++lq)
-    nready += (lq < (int)c->ready_marked.size() && c->ready_marked[lq]) ? 1 : 0;
-  FISDF_CHECK(nready == 0 || nready == nq, "fit_coulomb: mark every q of the call ready, or none");
-  const bool ready = nready > 0;
-  if (pipe) NL = std::min(NL, ready ? 2 : 3);  // aux[2] is the FFT stream
-  if (ready) NL = std::min(NL, 3);
-  int D = pipe ? std::min(nq, c->pipe_depth > 0 ? c->pipe_depth : default_pipe_depth(NL)) : 0;
-  if (pipe) {
-    // the ring outside the arena (nip rows per slot, whatever the ranks turn out to be); without
-    // the memory for it, the in-lane FFT
-    const size_t rb = sizeof(cplx) * (size_t)D * nip * ngrid;
-    if (rb > c->f_ring_bytes) {
-      if (c->f_ring) FISDF_HIP(hipFree(c->f_ring));
-      c->f_ring = nullptr;
-      c->f_ring_bytes = 0;
-      if (hipMalloc(&c->f_ring, rb) == hipSuccess) {
-        c->f_ring_bytes = rb;
-      } else {
-        (void)hipGetLastError();
-        c->f_ring = nullptr;
-        pipe = false;
-        D = 0;
-      }
-    }
-  }
-  if (pipe) {
-    while ((int)c->ev_q.size() < nq) {
-      hipEvent_t e;
-      FISDF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      c->ev_q.push_back(e);
-    }
-    while ((int)c->ev_free.size() < D) {
-      hipEvent_t e;
-      FISDF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      c->ev_free.push_back(e);
-    }
-  }
   bool any_piece = false;
-  for (int lq = 0; lq < nq; ++lq) any_piece = any_piece || piece_of(lq) != nullptr;
-  // all-to-all pieces of a mesh whose first FFT pass cannot read plane slices in place (no
-  // register kernel, plane too large for the LDS plane kernel): each FFT-issuing stream (the FFT
-  // stream, or every lane) unpacks its q's piece into a (nip, ngrid) buffer of its own first
-  const bool unpack = any_piece && !fft3d_reads_slices(mesh[0], mesh[1], mesh[2]);
-  const PlaneRef* planes = nullptr;
-  if (any_piece && !unpack) FISDF_TRY(plane_table(c, mesh, nip, &planes));
-  FISDF_CHECK(yT != nullptr || any_piece, "fit_coulomb: no y");
-  // sqrt(coulG(k_q+G) vol/N^2)  (:114-115 and the Parseval 1/N of :118), cached per q
-  const double wscale = vol / ((double)ngrid * ngrid);
-  static const int half_env = [] {
-    const char* e = getenv("FISDF_HALF_G");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  const bool half_on = (c->half_grid >= 0 ? c->half_grid : half_env) != 0;
-  auto half_of = [&](int sl) { return half_on && c->f_real[sl] != 0; };
-  auto weight_q = [&](hipStream_t st, int lq, const double** w) {
-    return get_weight(c, st, mesh, kmesh, a, h_qs[lq], wscale, half_of(s0 + lq), w);
-  };
-  auto slot_y = [&](int lq) { return c->f_ring + (long)(lq % D) * nip * ngrid; };
-  FISDF_TRY(fisdf_factor_x4_wait(c, nullptr));
-  int rmax = 0;
-  for (int lq = 0; lq < nq; ++lq) rmax = std::max(rmax, c->f_rank[s0 + lq]);
-  // minimum-norm slots transform all nip rows of y (the operator A^+ mixes every row)
-  auto cod_of = [&](int sl) { return sl < (int)c->f_cod.size() && c->f_cod[sl] != 0; };
-  int rfmax = rmax, ncod = 0;
-  for (int lq = 0; lq < nq; ++lq)
-    if (cod_of(s0 + lq)) {
-      rfmax = nip;
-      ++ncod;
-    }
-  // every q full rank (the production regime) and many q in the call: each q's W_PP =
-  // L^-H G L^-1 and its scatter run in its lane right after its HERK, overlapped with the other
-  // q's fit, instead of as a batched tail after the lanes join (the same kernel per output, batch
-  // 1: W_q unchanged bit for bit).  C3 on one GPU (36 q): 79.89 vs 80.21 ms/step; a k-shard's 4-5
-  // q: +0.6 ms per rank (the last q of each lane then waits for its own small GEMMs), so below
-  // kLaneWppMinQ q the batched tail stays.  FISDF_LANE_WPP: 0 never, 1 always
-  bool lane_wpp = lane_wpp_wanted(nq) && rmax == nip && ncod == 0;
-  for (int lq = 0; lq < nq && lane_wpp; ++lq) lane_wpp = c->f_rank[s0 + lq] == nip;
-  // split-K of each q's HERK from its own rank (not the call's largest), so a q's arithmetic
-  // does not depend on which other q share the call (1-GPU vs sharded builds agree bitwise)
-  const int ncu = num_cus(c->device);
-  auto ks_of = [&](int r, long K) { return pick_ksplit_herk(r, (int)K, ncu); };
-  int ks = 1;
-  for (int lq = 0; lq < nq; ++lq) ks = std::max(ks, ks_of(c->f_rank[s0 + lq], ngrid));
-  // a self-conjugate q is fitted on the prefix planes of its Hermitian G pairs (about half the
-  // grid): Re W = sum over one member of each pair with the pair's combined weight (half_of)
-  auto ncols_of = [&](int lq) -> long {
-    if (!half_of(s0 + lq)) return ngrid;
-    int m[3];
-    self_conjugate_m(kmesh, h_qs[lq], m);
-    return (long)half_prefix_planes(mesh[0], m[0]) * mesh[1] * mesh[2];
-  };
-  const long rr = (long)rmax * rmax;
-  const long sLi = (long)nblk * nb * nb;
-  Carver cv;
-  size_t oY[4], oU[4], oK[4], oTc[4];
-  for (int l = 0; l < NL; ++l) {
-    if (!pipe) oY[l] = cv.take(sizeof(cplx) * rfmax * ngrid);
-    oU[l] = cv.take(sizeof(cplx) * rmax * ngrid);
-    oK[l] = cv.take(sizeof(cplx) * (size_t)ks * rmax * rmax);
-    oTc[l] = cv.take(sizeof(cplx) * rr);
-  }
-  c->last_fit_lanes = NL;
-  c->last_fit_pipe = pipe ? D : 0;
-  size_t oP[4] = {0, 0, 0, 0};
-  if (unpack)
-    for (int l = 0; l < (pipe ? 1 : NL); ++l) oP[l] = cv.take(sizeof(cplx) * (size_t)nip * ngrid);
-  // W_PP = L^-H G L^-1 (two upper-triangular nip^3 GEMMs per q) split over K: 100 output tiles
-  // of 64 x 64 at C3 leave most CUs idle for ~180 us per GEMM, in every lane, for every q.  The
-  // split depends on nip only, the same in the lanes and in the batched tail (W_q bitwise equal
-  // between the 1-GPU and the k-sharded builds).  FISDF_WPP_KSPLIT (read per call; 1 = off)
-  const int wks = wpp_ksplit(nip);
-  // the record fisdf_fit_report reads (what is decided here; the FFT form and the asymmetric
-  // count are filled in where they are found)
-  {
-    bool all_full = rmax == nip;
-    for (int lq = 0; lq < nq && all_full; ++lq) all_full = c->f_rank[s0 + lq] == nip;
-    c->fit_report.assign(nq, fisdf_ctx::FitRec{});
-    for (int lq = 0; lq < nq; ++lq) {
-      int* v = c->fit_report[lq].v;
-      const int sl = s0 + lq, r = c->f_rank[sl];
-      v[0] = r;
-      v[1] = c->f_real[sl] ? 1 : 0;
-      v[2] = half_of(sl) ? 1 : 0;
-      v[4] = (int)ncols_of(lq);
-      v[6] = r == 0 ? -1 : cod_of(sl) ? 1 : r == nip ? 0 : 2;
-      v[7] = cod_of(sl) ? 1 : 0;
-      v[8] = lq % NL;
-      v[9] = lane_wpp ? 1 : all_full ? 0 : 2;
-      v[10] = (lane_wpp || all_full) ? wks : 1;
-      v[11] = piece_of(lq) ? (unpack ? 2 : 1) : 0;
-    }
-  }
-  const size_t oWk = wks > 1 ? cv.take(sizeof(cplx) * (size_t)NL * wks * rr) : 0;
-  size_t oG = cv.take(sizeof(cplx) * nq * rr);
-  size_t oT = cv.take(sizeof(cplx) * nq * rr);
-  size_t oS = cv.take(sizeof(cplx) * nq * rr);
-  size_t oMS = ncod ? cv.take(sizeof(cplx) * (size_t)ncod * rmax * nip) : 0;  // G M per min-norm slot
-  size_t oMT = ncod ? cv.take(sizeof(cplx) * nn) : 0;                  // M^H G M
-  void* base;
-  FISDF_TRY(arena_get(c, cv.off, &base));
-  char* b = (char*)base;
-  cplx* G = (cplx*)(b + oG);   // (nq, rmax, rmax): G_q in the leading r_q x r_q block, zero elsewhere
-  cplx* T = (cplx*)(b + oT);
-  cplx* S = (cplx*)(b + oS);
-  if (rmax == 0) {
-    FISDF_TRY(join_factors(c));
-    FISDF_HIP(hipMemsetAsync(Wq, 0, sizeof(cplx) * nq * nn, c->stream));
-    return 0;
-  }
-  hipStream_t lane_st[4] = {c->stream, nullptr, nullptr, nullptr};
-  hipStream_t fst = nullptr;  // the FFT stream of the pipelined mode
-  bool aux_used[3] = {false, false, false};
-  if (ready) {
-    // everything enqueued before the first piece landed (the y build, the arena's previous
-    // users) is complete at ev_ready[0]
-    FISDF_TRY(ensure_aux(c));
-    for (int l = 0; l < NL; ++l) {
-      lane_st[l] = c->aux[l];
-      aux_used[l] = true;
-      aux_fork(c, l);
-      FISDF_HIP(hipStreamWaitEvent(lane_st[l], c->ev_ready[0], 0));
-    }
-    FISDF_HIP(hipMemsetAsync(G, 0, sizeof(cplx) * nq * rr, lane_st[0]));
-    FISDF_HIP(hipEventRecord(c->ev_fork, lane_st[0]));
-    for (int l = 1; l < NL; ++l) FISDF_HIP(hipStreamWaitEvent(lane_st[l], c->ev_fork, 0));
-    if (pipe) {
-      fst = c->aux[2];
-      aux_used[2] = true;
-      aux_fork(c, 2);
-      FISDF_HIP(hipStreamWaitEvent(fst, c->ev_fork, 0));
-    }
-  } else if (NL > 1 || pipe) {
-    FISDF_HIP(hipMemsetAsync(G, 0, sizeof(cplx) * nq * rr, c->stream));
-    FISDF_TRY(ensure_aux(c));
-    FISDF_HIP(hipEventRecord(c->ev_fork, c->stream));
-    for (int l = 1; l < NL; ++l) {
-      lane_st[l] = c->aux[l - 1];
-      aux_used[l - 1] = true;
-      aux_fork(c, l - 1);
-      FISDF_HIP(hipStreamWaitEvent(lane_st[l], c->ev_fork, 0));
-    }
-    if (pipe) {
-      fst = c->aux[2];
-      aux_used[2] = true;
-      aux_fork(c, 2);
-      FISDF_HIP(hipStreamWaitEvent(fst, c->ev_fork, 0));
-    }
-  } else {
-    FISDF_HIP(hipMemsetAsync(G, 0, sizeof(cplx) * nq * rr, c->stream));
-  }
-  // Yhat_q = FFT(y_q[:, piv] * f_q) * w_q   (:99, :113-115, :118; rows in pivot order); the
-  // sharded build reads q in place from their all-to-all pieces (fisdf_set_y_slices) through a
-  // per-plane address table (plane-aligned slices)
-  // ub: the stream's unpack buffer (FFT stream 0, lane l -> l)
-  auto fft_q = [&](hipStream_t st, int lq, cplx* Yh, int ub) -> int {
-    const int sl = s0 + lq;
-    const int r = cod_of(sl) ? nip : c->f_rank[sl];
-    double kq[3], kd[3];
-    kpoint(kmesh, g, h_qs[lq], kq);
-    for (int i = 0; i < 3; ++i) kd[i] = g.a[i][0] * kq[0] + g.a[i][1] * kq[1] + g.a[i][2] * kq[2];
-    const double* wt = nullptr;
-    FISDF_TRY(weight_q(st, lq, &wt));
-    // a half-grid q: its transform pairs G with -G - m (m = 2 k_q, the phase exp(-i k_q.r) times
-    // a real input), so the FFT writes the prefix planes only and moves half of its intermediate
-    // (fft3d herm); m from the phase actually applied must match the pairing the weights use
-    int herm_m[3];
-    bool herm = half_of(sl);
-    if (herm) {
-      int m[3];
-      self_conjugate_m(kmesh, h_qs[lq], m);
-      for (int d = 0; d < 3; ++d) {
-        const double t = kd[d] / M_PI;
-        const long tm2 = std::lround(t);
-        herm = herm && std::fabs(t - (double)tm2) < 1e-9 &&
-               ((tm2 % mesh[d]) + mesh[d]) % mesh[d] == m[d] % mesh[d];
-        herm_m[d] = m[d];
-      }
-    }
-    const int* hm = herm ? herm_m : nullptr;
-    c->fit_report[lq].v[3] = fft3d_route(mesh[0], mesh[1], mesh[2], hm) == FFT_REG_HERM ? 1 : 0;
-    // y of this q stored real by the composite build's y kernel (fisdf_build_y_qs)
-    const bool y_real = yT != nullptr && lq < (int)c->y_real_slot.size() && c->y_real_slot[lq];
-    StageTimer tm(c, FISDF_ST_FFT, st);
-    const cplx* pc = piece_of(lq);
-    FISDF_CHECK(pc || yT, "fit_coulomb: q without y");
-#ifdef FISDF_EXP_NOFFT  // timing experiment only (wrong results)
-    return 0;
-#endif
-    if (pc && unpack) {  // piece -> (nip, ngrid) rows, stream-ordered before the FFT reads them
-      cplx* yb = (cplx*)(b + oP[ub]);
-      const char* src = (const char*)pc;
-      for (size_t p = 0; p + 1 < c->y_slices.size(); p += 2) {
-        const long g0 = c->y_slices[p], ng = c->y_slices[p + 1];
-        FISDF_CHECK(g0 + ng <= ngrid, "fit_coulomb: y slice out of the mesh");
-        if (ng == 0) continue;
-        FISDF_HIP(hipMemcpy2DAsync(yb + g0, sizeof(cplx) * ngrid, src, sizeof(cplx) * ng,
-                                   sizeof(cplx) * ng, nip, hipMemcpyDeviceToDevice, st));
-        src += sizeof(cplx) * (size_t)ng * nip;
-      }
-      pc = nullptr;
-      FISDF_TRY(fft3d(st, yb, ngrid, c->f_piv + (long)sl * nip, Yh, ngrid, r, mesh[0], mesh[1],
-                      mesh[2], kd, wt, nullptr, nullptr, hm));
-      return 0;
-    }
-    FISDF_CHECK(!(pc && y_real), "fit_coulomb: a real y slot with a y piece");
-    FISDF_TRY(fft3d(st, pc ? pc : yT + (long)lq * nip * ngrid, ngrid, c->f_piv + (long)sl * nip, Yh,
-                    ngrid, r, mesh[0], mesh[1], mesh[2], kd, wt, nullptr, pc ? planes : nullptr,
-                    hm, y_real));
-    return 0;
-  };
-  // FFT of q lq into its ring slot, after the lane that read the slot's previous q is done
-  auto enqueue_fft = [&](int lq) -> int {
-    if (lq >= nq || c->f_rank[s0 + lq] == 0) return 0;
-    if (lq >= D) FISDF_HIP(hipStreamWaitEvent(fst, c->ev_free[lq % D], 0));
-    if (ready) FISDF_HIP(hipStreamWaitEvent(fst, c->ev_ready[lq], 0));
-    FISDF_TRY(fft_q(fst, lq, slot_y(lq), 0));
-    FISDF_HIP(hipEventRecord(c->ev_q[lq], fst));
-    return 0;
-  };
-  if (pipe)
-    for (int lq = 0; lq < D; ++lq) FISDF_TRY(enqueue_fft(lq));
   for (int lq = 0; lq < nq; ++lq) {
-    const int ln = lq % NL;
-    hipStream_t st = lane_st[ln];
-    cplx* Yh = pipe ? slot_y(lq) : (cplx*)(b + oY[ln]);
-    cplx* U = (cplx*)(b + oU[ln]);
-    cplx* kw = (cplx*)(b + oK[ln]);
-    cplx* Tc = (cplx*)(b + oTc[ln]);
-    const int q = h_qs[lq];
-    const int sl = s0 + lq;  // factor slot
-    const int r = c->f_rank[sl];
-    if (r == 0) {
-      if (pipe) FISDF_TRY(enqueue_fft(lq + D));
-      continue;
-    }
-    const int* piv = c->f_piv + (long)sl * nip;
-    const cplx* Lp = c->f_Lp + (long)sl * nn;
-    const bool real_q = c->f_real[sl];
-    const cplx* Linv = c->f_Linv + (long)sl * sLi;
-    (void)piv;
-    if (pipe) {
-      FISDF_HIP(hipStreamWaitEvent(st, c->ev_q[lq], 0));
-    } else {
-      if (ready) FISDF_HIP(hipStreamWaitEvent(st, c->ev_ready[lq], 0));
-      FISDF_TRY(fft_q(st, lq, Yh, ln));
-    }
-    cplx* Uq = U;  // where L^{-1} Yh lands
-    const long ncol = ncols_of(lq);  // grid columns fitted (half for a self-conjugate q)
-    // L^-1, Q, ...: the slots built first need only their own (ev_fac_early); a lane's later q
-    // wait for all of them
-    if (c->f_fac_unjoined)
-      FISDF_HIP(hipStreamWaitEvent(
-          st, (sl < c->f_early && !cod_of(sl)) ? c->ev_fac_early : c->ev_fac, 0));
-    {
-      // U = L^{-1} Yh   (fit, factored order; (x4_q)_PP = L L^H): one GEMM (timed kernel-exact)
-      // on a full-rank q and on a minimum-norm q; the basic solution of a rank-deficient q
-      // (FISDF_FIT_BASIC) substitutes block by block
-      const bool one_gemm = cod_of(sl) || r == nip;
-      StageTimer tm(c, FISDF_ST_TRSM, st, one_gemm);
-      if (cod_of(sl)) {  // U = A^+ Yh[P]: the minimum-norm operator over all nip rows
-        FISDF_TRY(zgemm(st, OP_N, OP_N, r, (int)ncol, nip, ONE, c->f_M + (long)sl * nn, nip, 0, Yh,
-                        ngrid, 0, ZERO, U, ngrid, 0, 1, 1, nullptr, EPI_NONE, nullptr,
-                        real_q ? GEMM_A_REAL : GEMM_FULL));
-        Uq = U;
-      } else if (r == nip) {  // one lower-triangular GEMM with L^{-1}
-#ifdef FISDF_EXP_NOREALTRSM  // timing experiment only (wrong results)
-        if (real_q) { Uq = U; } else
-#endif
-        FISDF_TRY(zgemm(st, OP_N, OP_N, nip, (int)ncol, nip, ONE, c->f_Li + (long)sl * nn, nip, 0,
-                        Yh, ngrid, 0, ZERO, U, ngrid, 0, 1, 1, nullptr, EPI_NONE, nullptr,
-                        GEMM_A_LOWER | (real_q ? GEMM_A_REAL : GEMM_FULL)));
-        Uq = U;
-      } else {
-        FISDF_TRY(trsm_blocked(st, 1, Lp, nip, 0, r, Linv, 0, nb, Yh, ngrid, 0, U, ngrid,
-                               0, (int)ncol, 1, real_q ? 1 : 0));
-      }
-    }
-    cplx* scratch = Uq == U ? Yh : U;
-    {
-      StageTimer tm(c, FISDF_ST_HERK, st, true);
-      // G = U U^H  (:121 by Parseval)
-      FISDF_TRY(herk(st, r, (int)ncol, 1.0, Uq, ngrid, G + lq * rr, rmax, ks_of(r, ncol), kw,
-                     real_q ? GEMM_RE_ONLY : GEMM_FULL));
-    }
-    if (real_q) {
-      StageTimer tm(c, FISDF_ST_SMALL, st);
-      {
-        // Im(G) = Im(sum over the weight-asymmetric G only): every other (G, G') pair cancels
-        const fisdf_ctx::Asym* as = nullptr;
-        if (half_of(sl)) {
-          // half grid: one member of each asymmetric pair, Im W = Im(U_A diag(f) U_A^H)
-          FISDF_TRY(get_asym_half(c, st, mesh, kmesh, a, q, wscale, &as));
-          c->fit_report[lq].v[5] = as->n;
-          // scratch holds r x ngrid: the plain and the scaled copy of at most ngrid / 2 listed
-          // columns at a time (one pass unless more than half the grid is listed, which takes a
-          // mesh whose planes are all self-paired, n0 <= 2)
-          const int cap = (int)std::max(1L, ngrid / 2);
-          for (int o = 0; o < as->n; o += cap) {
-            const int na = std::min(cap, as->n - o);
-            cplx* plain = scratch;
-            cplx* scaled = scratch + (long)r * na;
-            FISDF_TRY(gather_cols_scaled(st, Uq, ngrid, r, as->idx + o, nullptr, na, plain));
-            FISDF_TRY(gather_cols_scaled(st, Uq, ngrid, r, as->idx + o, as->f + o, na, scaled));
-            FISDF_TRY(zgemm(st, OP_N, OP_C, r, r, na, ONE, scaled, na, 0, plain, na, 0, ZERO, Tc,
-                            rmax, 0, 1, std::min(ks_of(r, ncol), std::max(1, na / 256)), kw));
-            FISDF_TRY(add_imag(st, G + lq * rr, rmax, Tc, rmax, r));
-          }
-        } else {
-          const double* wt = nullptr;
-          FISDF_TRY(weight_q(st, lq, &wt));
-          FISDF_TRY(get_asym(c, st, mesh, kmesh, a, q, wt, &as));
-          c->fit_report[lq].v[5] = as->n;
-          if (as->n > 0) {
-            FISDF_TRY(gather_cols(st, Uq, ngrid, r, as->idx, as->n, scratch));
-            FISDF_TRY(herk(st, r, as->n, 1.0, scratch, as->n, Tc, rmax,
-                           std::min(ks_of(r, ncol), std::max(1, as->n / 256)), kw));
-            FISDF_TRY(add_imag(st, G + lq * rr, rmax, Tc, rmax, r));
-          }
-        }
-      }
-    }
-    if (pipe) {  // this lane is done with the ring slot: the FFT D q ahead may overwrite it
-      FISDF_HIP(hipEventRecord(c->ev_free[lq % D], st));
-      FISDF_TRY(enqueue_fft(lq + D));
-    }
-    if (lane_wpp) {  // W_PP = L^-H G L^-1 of this q (S = L^-H G, W_PP = L^-H S^H), scattered
-      StageTimer tm(c, FISDF_ST_SMALL, st);
-      const cplx* Lf = c->f_Li + (long)sl * nn;
-      cplx* wk = wks > 1 ? (cplx*)(b + oWk) + (long)ln * wks * rr : nullptr;
-      FISDF_TRY(zgemm(st, OP_C, OP_N, nip, nip, nip, ONE, Lf, nip, 0, G + lq * rr, rmax, 0, ZERO,
-                      S + lq * rr, rmax, 0, 1, wks, wk, EPI_NONE, nullptr, GEMM_A_UPPER));
-      FISDF_TRY(zgemm(st, OP_C, OP_C, nip, nip, nip, ONE, Lf, nip, 0, S + lq * rr, rmax, 0, ZERO,
-                      T + lq * rr, rmax, 0, 1, wks, wk, EPI_NONE, nullptr, GEMM_A_UPPER));
-      FISDF_TRY(scatter_w(st, T + lq * rr, rmax, rr, rmax, c->f_piv + (long)sl * nip,
-                          c->f_rank_dev + sl, Wq + lq * nn, nip, 1));
-    }
+    nready += (lq < (int)c->ready_marked.size() && c->ready_marked[lq]) ? 1 : 0;
+    any_piece = any_piece || fit_piece(c, lq) != nullptr;
   }
-  // join the lanes (and the FFT stream: that keeps the arena reuse ordered) before the batched
-  // small stage on the main stream
-  // (this join is what makes fisdf_build's build_return(c, yT) right after this call safe: every
-  // FFT / lane read of y is ordered before the caller's stream-ordered free on c->stream)
-  for (int i = 0; i < 3; ++i)
-    if (aux_used[i]) FISDF_TRY(aux_join(c, i));
-  FISDF_TRY(join_factors(c));
-  if (!lane_wpp) {
-    StageTimer tm(c, FISDF_ST_SMALL);
-    // W_PP = L^{-H} G L^{-1} for all q of the shard at once (L padded with identity, G with
-    // zeros beyond each rank):  T = L^{-H} G ; S = L^{-H} T^H ; W_PP = S^H ; scatter by pivots
-    const cplx* Lp0 = c->f_Lp + (long)s0 * nn;
-    const cplx* Li0 = c->f_Linv + (long)s0 * sLi;
-    // minimum-norm slots: G M first (the batched back-substitutions below overwrite G)
-    for (int lq = 0, j = 0; lq < nq && ncod; ++lq) {
-      const int sl = s0 + lq, r = c->f_rank[sl];
-      if (!cod_of(sl)) continue;
-      FISDF_TRY(zgemm(c->stream, OP_N, OP_N, r, nip, r, ONE, G + lq * rr, rmax, 0,
-                      c->f_M + (long)sl * nn, nip, 0, ZERO, (cplx*)(b + oMS) + (long)j++ * rmax * nip,
-                      nip, 0, 1));
-    }
-    bool all_full = rmax == nip;
-    for (int lq = 0; lq < nq && all_full; ++lq) all_full = c->f_rank[s0 + lq] == nip;
-    if (all_full) {
-      // with L^{-1} at hand, two batched GEMMs whose A = L^{-H} is upper triangular (each
-      // M-tile starts its K loop at its own row: half the flops of dense GEMMs):
-      //   S = L^{-H} G,  W_PP = L^{-H} S^H  (= L^{-H} G L^{-1}, G Hermitian)
-      const cplx* Lf = c->f_Li + (long)s0 * nn;
-      if (wks > 1) {
-        // the lanes' split workspace, NL q at a time (per-q arithmetic as in the lanes)
-        cplx* wk = (cplx*)(b + oWk);
-        for (int z0 = 0; z0 < nq; z0 += NL) {
-          const int nz = std::min(NL, nq - z0);
-          FISDF_TRY(zgemm(c->stream, OP_C, OP_N, nip, nip, nip, ONE, Lf + (long)z0 * nn, nip, nn,
-                          G + z0 * rr, rmax, rr, ZERO, S + z0 * rr, rmax, rr, nz, wks, wk, EPI_NONE,
-                          nullptr, GEMM_A_UPPER));
-          FISDF_TRY(zgemm(c->stream, OP_C, OP_C, nip, nip, nip, ONE, Lf + (long)z0 * nn, nip, nn,
-                          S + z0 * rr, rmax, rr, ZERO, T + z0 * rr, rmax, rr, nz, wks, wk, EPI_NONE,
-                          nullptr, GEMM_A_UPPER));
-        }
-      } else {
-        FISDF_TRY(zgemm(c->stream, OP_C, OP_N, nip, nip, nip, ONE, Lf, nip, nn, G, rmax, rr, ZERO,
-                        S, rmax, rr, nq, 1, nullptr, EPI_NONE, nullptr, GEMM_A_UPPER));
-        FISDF_TRY(zgemm(c->stream, OP_C, OP_C, nip, nip, nip, ONE, Lf, nip, nn, S, rmax, rr, ZERO,
-                        T, rmax, rr, nq, 1, nullptr, EPI_NONE, nullptr, GEMM_A_UPPER));
-      }
-    } else {
-      FISDF_TRY(trsm_blocked(c->stream, 0, Lp0, nip, nn, rmax, Li0, sLi, nb, G, rmax, rr,
-                             T, rmax, rr, rmax, nq));
-      FISDF_TRY(conj_transpose(c->stream, T, rmax, rr, G, nq));
-      FISDF_TRY(trsm_blocked(c->stream, 0, Lp0, nip, nn, rmax, Li0, sLi, nb, G, rmax, rr,
-                             S, rmax, rr, rmax, nq));
-      FISDF_TRY(conj_transpose(c->stream, S, rmax, rr, T, nq));
-    }
-    FISDF_TRY(scatter_w(c->stream, T, rmax, rr, rmax, c->f_piv + (long)s0 * nip,
-                        c->f_rank_dev + s0, Wq, nip, nq));
-    // minimum-norm slots: W_PP = M^H (G M) (nip x nip: z[P] = M^H U) replaces the above
-    for (int lq = 0, j = 0; lq < nq && ncod; ++lq) {
-      const int sl = s0 + lq, r = c->f_rank[sl];
-      if (!cod_of(sl)) continue;
-      const cplx* MS = (cplx*)(b + oMS) + (long)j++ * rmax * nip;
-      cplx* MT = (cplx*)(b + oMT);
-      const cplx* Mq = c->f_M + (long)sl * nn;
-      FISDF_TRY(zgemm(c->stream, OP_C, OP_N, nip, nip, r, ONE, Mq, nip, 0, MS, nip, 0, ZERO, MT,
-                      nip, 0, 1));
-      FISDF_TRY(scatter_w(c->stream, MT, nip, 0, nip, c->f_piv + (long)sl * nip, c->f_nip_dev,
-                          Wq + lq * nn, nip, 1));
-    }
+  FISDF_CHECK(nready == 0 || nready == nq, "fit_coulomb: mark every q of the call ready, or none");
+  fit_plan_lanes(p, nq, mesh, c->lanes > 0 ? c->lanes : env_fit_lanes(),
+                 c->pipe_mode >= 0 ? c->pipe_mode : env_fit_pipe(), c->pipe_depth, nready > 0,
+                 any_piece);
+  FISDF_TRY(fit_ring(c, p, nip, f.ngrid));
+  if (any_piece && !p.unpack) FISDF_TRY(plane_table(c, mesh, nip, &f.planes));
+  FISDF_CHECK(f.yT != nullptr || any_piece, "fit_coulomb: no y");
+  const bool half_on = (c->half_grid >= 0 ? c->half_grid : env_half_grid()) != 0;
+  FISDF_TRY(fisdf_factor_x4_wait(c, nullptr));
+  fit_plan_ranks(p, nip, mesh, kmesh, h_qs, f.s0, c->f_rank, c->f_real, c->f_cod, half_on,
+                 num_cus(c->device));
+  f.o = fit_layout(p, nip, f.ngrid);
+  f.rr = (long)p.rmax * p.rmax;
+  c->last_fit_lanes = p.NL;
+  c->last_fit_pipe = p.D;
+  fit_report_fill(c, p);
+  void* base;
+  FISDF_TRY(arena_get(c, f.o.total, &base));
+  f.b = (char*)base;
+  f.G = (cplx*)(f.b + f.o.oG);
+  f.T = (cplx*)(f.b + f.o.oT);
+  f.S = (cplx*)(f.b + f.o.oS);
+  if (p.rmax == 0) {
+    FISDF_TRY(join_factors(c));
+    FISDF_HIP(hipMemsetAsync(f.Wq, 0, sizeof(cplx) * nq * f.nn, c->stream));
+    return 0;
   }
+  FISDF_TRY(fit_fork(f));
+  if (p.pipe)
+    for (int lq = 0; lq < p.D; ++lq) FISDF_TRY(fit_enqueue_fft(f, lq));
+  for (int lq = 0; lq < nq; ++lq) FISDF_TRY(fit_q(f, lq));
+  FISDF_TRY(fit_join(f));
+  if (!p.lane_wpp) FISDF_TRY(fit_tail(f));
   return 0;
 }
 

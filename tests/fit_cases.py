@@ -531,8 +531,15 @@ def rank_runs():
 
 
 def y_runs():
-    return [Run("even222_w0_n40", 1, 1, 0, -1, 0, LSTSQ, y) for y in ("slices", "ready")] + \
-           [Run("axes222_w0_n5", 1, 1, 0, -1, 0, LSTSQ, "slices")]
+    """The default lanes and pipe for every y source, then the forks only marks reach, on the
+    eight q of even222_w0_n40: every lane on an aux stream (3 lanes, no pipe), the ready cap (4
+    asked, 3 run), the ready-and-pipe cap (3 asked, 2 run beside the FFT stream, ring of 4), and
+    pieces with the ring (fisdf_set_y_slices marks its q ready as well, so 3 asked, 2 run)."""
+    n = "even222_w0_n40"
+    return [Run(n, 1, 1, 0, -1, 0, LSTSQ, y) for y in ("slices", "ready")] + \
+           [Run("axes222_w0_n5", 1, 1, 0, -1, 0, LSTSQ, "slices"),
+            Run(n, 1, 1, 3, 0, 0, LSTSQ, "ready"), Run(n, 1, 1, 4, 0, 0, LSTSQ, "ready"),
+            Run(n, 1, 1, 3, 1, 0, LSTSQ, "ready"), Run(n, 1, 1, 3, 1, 0, LSTSQ, "slices")]
 
 
 def split_runs():
