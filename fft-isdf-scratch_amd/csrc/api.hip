@@ -4086,6 +4086,159 @@ int fisdf_get_eri_fft(fisdf_ctx* c, const int mesh[3], const double a[9], const 
   return 0;
 }
 
+// ---- GTH pseudopotential and nuclear-attraction matrices (PySCF FFTDF.get_pp / get_nuc); the
+// kernels and the plan are in pp.hip -----------------------------------------------------------------
+int fisdf_pp_nproj(const fisdf_pp_atom* atoms, int natm) {
+  if (pp_check_table(atoms, natm, "pp_nproj") != 0) return -1;
+  const long rows = pp_rows(atoms, 0, natm);
+  return rows < (1L << 31) ? (int)rows : -1;
+}
+
+int fisdf_pp_plan(int nao, long ngrid, int nk, int np, const fisdf_pp_atom* atoms, int natm,
+                  int with_nonlocal, long work_bytes, int* h_run_len, int* h_nrun, int* h_mtiles,
+                  int* h_ptiles, int* h_nchunk, int* h_chunk_rows, long* h_bytes) {
+  FISDF_CHECK(atoms == nullptr || pp_check_table(atoms, natm, "pp_plan") == 0,
+              "pp_plan: the atom table is refused");
+  PpPlan p;
+  pp_plan(nao, ngrid, nk, atoms, atoms ? natm : 0, with_nonlocal, work_bytes, &p);
+  FISDF_CHECK(p.run_len > 0, "pp_plan: a size is out of range");
+  if (h_run_len) *h_run_len = p.run_len;
+  if (h_nrun) *h_nrun = p.nrun;
+  if (h_mtiles) *h_mtiles = p.mtiles;
+  if (h_ptiles) *h_ptiles = ((atoms ? p.nproj : np) + kPpPT - 1) / kPpPT;
+  if (h_nchunk) *h_nchunk = p.ok ? p.nchunk : 0;
+  if (h_chunk_rows) *h_chunk_rows = p.ok ? p.chunk_rows : 0;
+  if (h_bytes) *h_bytes = p.ok ? p.bytes : 0;
+  return 0;
+}
+
+int fisdf_vloc_g(fisdf_ctx* c, const int mesh[3], const double a[9], const fisdf_pp_atom* atoms,
+                 int natm, void* vgv) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(vgv, "vloc_g: null pointer");
+  long ngl = 0;
+  FISDF_TRY(potential_check(mesh, a, 1, &ngl));
+  FISDF_TRY(pp_check_table(atoms, natm, "vloc_g"));
+  CellGeom g;
+  lattice(a, g);
+  std::vector<double> tab;
+  pp_vloc_table(atoms, natm, &tab);
+  void* base;
+  FISDF_TRY(arena_get(c, sizeof(double) * tab.size(), &base));
+  FISDF_TRY(upload_bytes(c, tab.data(), sizeof(double) * tab.size(), base));
+  return vloc_g(c->stream, mesh, g, (const double*)base, natm, 1.0, 0, (cplx*)vgv);
+}
+
+int fisdf_gth_projectors(fisdf_ctx* c, const int mesh[3], const double a[9], const double h_k[3],
+                         const fisdf_pp_atom* atoms, int natm, int a0, int a1, void* rowsv) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(rowsv && h_k, "gth_projectors: null pointer");
+  FISDF_CHECK(std::isfinite(h_k[0]) && std::isfinite(h_k[1]) && std::isfinite(h_k[2]),
+              "gth_projectors: bad k-point");
+  long ngl = 0;
+  FISDF_TRY(potential_check(mesh, a, 1, &ngl));
+  FISDF_TRY(pp_check_table(atoms, natm, "gth_projectors"));
+  FISDF_CHECK(0 <= a0 && a0 < a1 && a1 <= natm, "gth_projectors: bad atom range");
+  std::vector<PpBlock> blk;
+  pp_blocks(atoms, a0, a1, &blk);
+  FISDF_CHECK(!blk.empty(), "gth_projectors: the atoms have no projectors");
+  CellGeom g;
+  lattice(a, g);
+  void* base;
+  FISDF_TRY(arena_get(c, sizeof(PpBlock) * blk.size(), &base));
+  FISDF_TRY(upload_bytes(c, blk.data(), sizeof(PpBlock) * blk.size(), base));
+  return gth_projectors(c->stream, mesh, g, h_k, (const PpBlock*)base, (int)blk.size(),
+                        (cplx*)rowsv);
+}
+
+int fisdf_pp_overlap(fisdf_ctx* c, const void* tv, int np, const void* fv, int nao,
+                     const int mesh[3], const double* h_kd, double scale, void* cv) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(tv && fv && cv && mesh, "pp_overlap: null pointer");
+  FISDF_CHECK(np >= 1 && nao >= 1 && nao <= kKfftMaxNao, "pp_overlap: sizes out of range");
+  FISDF_CHECK(mesh[0] >= 1 && mesh[1] >= 1 && mesh[2] >= 1, "pp_overlap: bad mesh");
+  const long ngl = (long)mesh[0] * mesh[1] * mesh[2];
+  FISDF_CHECK(ngl < (1L << 31), "pp_overlap: mesh too large");
+  int run_len = 0, nrun = 0;
+  pp_overlap_split(ngl, &run_len, &nrun);
+  void* base;
+  FISDF_TRY(arena_get(c, sizeof(cplx) * (size_t)nrun * np * nao, &base));
+  return pp_overlap(c->stream, (const cplx*)tv, np, (const cplx*)fv, nao, mesh, h_kd, scale,
+                    (cplx*)cv, (cplx*)base);
+}
+
+int fisdf_get_pp(fisdf_ctx* c, const void* fv, long f_kstride, int nk, const double* h_kpts,
+                 const int mesh[3], const double a[9], int nao, const fisdf_pp_atom* atoms,
+                 int natm, int with_nonlocal, long work_bytes, void* outv) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(fv && h_kpts && outv, "get_pp: null pointer");
+  FISDF_CHECK(nk >= 1 && nk <= 65535, "get_pp: 1 to 65535 k-points");
+  FISDF_CHECK(nao >= 1 && nao <= kKfftMaxNao, "get_pp: nao must be in [1, 32768]");
+  FISDF_CHECK(work_bytes >= 0, "get_pp: negative work_bytes");
+  for (int i = 0; i < 3 * nk; ++i) FISDF_CHECK(std::isfinite(h_kpts[i]), "get_pp: bad k-point");
+  long ngl = 0;
+  FISDF_TRY(potential_check(mesh, a, 1, &ngl));
+  FISDF_CHECK(f_kstride >= ngl * nao, "get_pp: f_kstride below ngrid * nao");
+  FISDF_TRY(pp_check_table(atoms, natm, "get_pp"));
+  PpPlan p;
+  pp_plan(nao, ngl, nk, atoms, natm, with_nonlocal, work_bytes, &p);
+  FISDF_CHECK(p.ok, "get_pp: work_bytes below the projector rows of one atom");
+  // the FFT's own checks of the mesh, for the potential's row and for the largest chunk
+  FISDF_TRY(fft3d_check(std::max(1, p.chunk_rows), mesh[0], mesh[1], mesh[2]));
+  CellGeom g;
+  lattice(a, g);
+  const double vol = cell_volume(a);
+  const int ngrid = (int)ngl;
+  void* base;
+  FISDF_TRY(arena_get(c, (size_t)p.bytes, &base));
+  auto at = [&](long off) { return (char*)base + off; };
+  cplx* v = (cplx*)at(p.off_v);
+  cplx* rows = (cplx*)at(p.off_rows);
+  cplx* part = (cplx*)at(p.off_part);
+  cplx* cc = (cplx*)at(p.off_c);
+  double* tab = (double*)at(p.off_tab);
+  PpBlock* dblk = (PpBlock*)at(p.off_blk);
+  cplx* out = (cplx*)outv;
+  // the local part: conj(V_G) / vol, one forward transform = conj(v), its real part, the Gram
+  std::vector<double> htab;
+  pp_vloc_table(atoms, natm, &htab);
+  FISDF_TRY(upload_bytes(c, htab.data(), sizeof(double) * htab.size(), tab));
+  FISDF_TRY(vloc_g(c->stream, mesh, g, tab, natm, 1.0 / vol, 1, v));
+  FISDF_TRY(fft3d(c->stream, v, ngl, nullptr, v, ngl, 1, mesh[0], mesh[1], mesh[2], nullptr, nullptr,
+                  nullptr));
+  FISDF_TRY(zero_imag(c->stream, v, ngl));
+  FISDF_TRY(weighted_gram(c->stream, (const cplx*)fv, f_kstride, nk, ngrid, nao, v, 1, 0,
+                          vol / (double)ngl, out, (cplx*)at(p.off_gram), p.gram_elems));
+  // the non-local part, k by k and chunk by chunk: every chunk's channels lie one behind the other
+  std::vector<int> blk0(p.nchunk + 1, 0);
+  for (int ch = 0; ch < p.nchunk; ++ch) {
+    std::vector<PpBlock> blk;
+    pp_blocks(atoms, p.chunk_a[ch], p.chunk_a[ch + 1], &blk);
+    FISDF_TRY(upload_bytes(c, blk.data(), sizeof(PpBlock) * blk.size(), dblk + blk0[ch]));
+    blk0[ch + 1] = blk0[ch] + (int)blk.size();
+  }
+  for (int k = 0; k < nk; ++k) {
+    const double* kp = h_kpts + 3 * k;
+    double kd[3];
+    for (int d = 0; d < 3; ++d) kd[d] = g.a[d][0] * kp[0] + g.a[d][1] * kp[1] + g.a[d][2] * kp[2];
+    const bool gamma = std::fabs(kp[0]) + std::fabs(kp[1]) + std::fabs(kp[2]) < 1e-9;
+    cplx* out_k = out + (long)k * nao * nao;
+    for (int ch = 0; ch < p.nchunk; ++ch) {
+      const int nb = blk0[ch + 1] - blk0[ch];
+      const int np = (int)pp_rows(atoms, p.chunk_a[ch], p.chunk_a[ch + 1]);
+      if (nb == 0) continue;
+      FISDF_TRY(gth_projectors(c->stream, mesh, g, kp, dblk + blk0[ch], nb, rows));
+      FISDF_TRY(fft3d(c->stream, rows, ngl, nullptr, rows, ngl, np, mesh[0], mesh[1], mesh[2],
+                      nullptr, nullptr, nullptr));
+      FISDF_TRY(pp_overlap(c->stream, rows, np, (const cplx*)fv + (long)k * f_kstride, nao, mesh,
+                           gamma ? nullptr : kd, 1.0 / (double)ngl, cc, part));
+      FISDF_TRY(pp_vnl(c->stream, cc, nao, dblk + blk0[ch], nb, out_k));
+    }
+    if (gamma) FISDF_TRY(zero_imag(c->stream, out_k, (long)nao * nao));
+  }
+  return 0;
+}
+
 // ---- A8 -----------------------------------------------------------------------
 static int get_k_block(fisdf_ctx* c, const void* Xv, const double* Ws_rows, long ws_Rstride,
                        const void* dmsv, int nset, int nip, int nao, const int kmesh[3],

@@ -257,6 +257,9 @@ int fft3d(hipStream_t s, const cplx* in, long in_ld, const int* rowidx, cplx* ou
 // radix-7/11/13 instantiation
 enum FftRoute { FFT_REG = 0, FFT_REG_HERM = 1, FFT_PLANE = 2, FFT_AXES = 3, FFT_BIG = 16 };
 int fft3d_route(int n0, int n1, int n2, const int* herm);
+// every host-side check fft3d makes of a plain transform of `rows` rows on the mesh, with nothing
+// launched: 0, or the error fft3d would raise
+int fft3d_check(int rows, int n0, int n1, int n2);
 // whether fft3d takes sliced input for this mesh (its first pass is a per-plane kernel)
 bool fft3d_reads_slices(int n0, int n1, int n2);
 // whether fft3d takes real input (in_real: rows of doubles at the same strides) for this mesh

@@ -813,6 +813,25 @@ int fft3d_route(int n0, int n1, int n2, const int* herm) {
   return (plane_kernel_lds(n1, n2) <= 96 * 1024 ? FFT_PLANE : FFT_AXES) | (big ? FFT_BIG : 0);
 }
 
+int fft3d_check(int rows, int n0, int n1, int n2) {
+  FISDF_CHECK(n0 >= 1 && n1 >= 1 && n2 >= 1, "fft: mesh dimension must be in [1, 64]");
+  const int route = fft3d_route(n0, n1, n2, nullptr) & ~FFT_BIG;
+  if (route == FFT_REG) {
+    FISDF_CHECK((long)rows * n0 < (1L << 31) && (long)rows * n1 * n2 < (1L << 38), "fft: too large");
+    return 0;
+  }
+  AxisGeom geom;
+  for (int axis = route == FFT_PLANE ? 0 : 2; axis >= 0; --axis)
+    FISDF_TRY(axis_geom(rows, axis, n0, n1, n2, &geom));
+  if (route == FFT_PLANE) {
+    Stages st1, st2;
+    FISDF_CHECK(n1 <= MAXN && n2 <= MAXN && factorize(n1, st1) && factorize(n2, st2),
+                "fft: mesh dimension must be <= 64 and factor into 2,3,5,7,11,13");
+    FISDF_CHECK((long)rows * n0 < (1L << 31), "fft: too many planes");
+  }
+  return 0;
+}
+
 int fft3d(hipStream_t s, const cplx* in, long in_ld, const int* rowidx, cplx* out, long out_ld,
           int rows, int n0, int n1, int n2, const double* kd, const double* weight, cplx* /*work*/,
           const PlaneRef* planes, const int* herm, bool in_real) {

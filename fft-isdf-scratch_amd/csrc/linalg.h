@@ -3,6 +3,8 @@
 
 #include <vector>
 
+struct fisdf_pp_atom;  // include/fisdf.h
+
 namespace fisdf {
 
 struct CellGeom {
@@ -300,5 +302,59 @@ struct EriFftPlan {
 };
 void eri_fft_plan(int n1, int n2, int n3, int n4, int npair, long ngrid, long work_bytes,
                   EriFftPlan* p);
+
+// ---- GTH pseudopotential matrices (pp.hip; PySCF FFTDF.get_pp / get_nuc): the local part's V_G,
+// the separable projectors of one k-point, their overlaps with the Bloch AOs, c^H h c ----
+constexpr int kPpGT = 64;        // grid points per step of the overlap kernel
+constexpr int kPpMT = 32;        // AO columns per workgroup of the overlap
+constexpr int kPpPT = 16;        // projector rows per workgroup of the overlap (two per thread)
+constexpr long kPpRuns = 256;    // grid runs the overlap aims at
+constexpr int kPpVlocCols = 9;   // doubles per atom of the local table: R, Z, rloc, c1..c4
+// One (atom, l) channel of the table: its n (2 l + 1) projector rows start at row0 of the rows
+// in hand (a chunk of whole atoms), row = row0 + i (2 l + 1) + mm
+struct PpBlock {
+  double R[3], rl;
+  double h[9];
+  int l, n, row0, pad;
+};
+// the table's checks (nl <= 4, n[l] <= 3, nexp <= 4, counts >= 0, rloc and the r_l read > 0) as an
+// error naming `who`; pp_rows: the projector rows of atoms [a0, a1) of a checked table
+int pp_check_table(const fisdf_pp_atom* atoms, int natm, const char* who);
+long pp_rows(const fisdf_pp_atom* atoms, int a0, int a1);
+// the host tables: kPpVlocCols doubles per atom (a bare nucleus: rloc = 0, c = 0, for which the
+// pseudopotential's formulas give -4 pi Z / G^2 and 0 at G = 0); the channels of atoms [a0, a1)
+void pp_vloc_table(const fisdf_pp_atom* atoms, int natm, std::vector<double>* tab);
+void pp_blocks(const fisdf_pp_atom* atoms, int a0, int a1, std::vector<PpBlock>* blocks);
+// out[G] = scale V_G (conj_out: conjugated) over the mesh; tab: device, pp_vloc_table's
+int vloc_g(hipStream_t s, const int mesh[3], const CellGeom& g, const double* tab, int natm,
+           double scale, int conj_out, cplx* out);
+// rows[row][G] = conj(beta_row(G; k)) for the channels blocks[0..nblocks) (device)
+int gth_projectors(hipStream_t s, const int mesh[3], const CellGeom& g, const double k[3],
+                   const PpBlock* blocks, int nblocks, cplx* rows);
+// c[p][m] = scale sum_g t[p][g] exp(-i frac(g).kd) f[g][m] (kd null: no phase); the grid in
+// *nrun runs of *run_len points (pp_overlap_split, from ngrid alone) whose partial blocks are
+// summed in run order; part: nrun np nao complex elements
+void pp_overlap_split(long ngrid, int* run_len, int* nrun);
+int pp_overlap(hipStream_t s, const cplx* t, int np, const cplx* f, int nao, const int mesh[3],
+               const double* kd, double scale, cplx* c, cplx* part);
+// out[m][n] += sum over the channels, mm, i, j of conj(c[(i, mm)][m]) h[i][j] c[(j, mm)][n], the
+// terms added to out's value one by one in table order (so the result does not depend on how the
+// channels are spread over calls)
+int pp_vnl(hipStream_t s, const cplx* c, int nao, const PpBlock* blocks, int nblocks, cplx* out);
+// What fisdf_get_pp does for given sizes and a byte budget for one k-point's projector rows (0:
+// kKfftWorkBytes): chunks of whole atoms [chunk_a[i], chunk_a[i + 1]) of at most chunk_rows rows;
+// ok = 0 when an atom's own rows exceed the budget or a size is out of range.  The arena's layout
+// (byte offsets) and total.
+struct PpPlan {
+  int ok = 0;
+  int run_len = 0, nrun = 0, mtiles = 0;
+  int nproj = 0, nchunk = 0, chunk_rows = 0, max_blocks = 0;
+  std::vector<int> chunk_a;
+  long gram_elems = 0;
+  long off_v = 0, off_gram = 0, off_rows = 0, off_part = 0, off_c = 0, off_tab = 0, off_blk = 0;
+  long bytes = 0;
+};
+void pp_plan(int nao, long ngrid, int nk, const fisdf_pp_atom* atoms, int natm, int with_nonlocal,
+             long work_bytes, PpPlan* p);
 
 }  // namespace fisdf

@@ -113,6 +113,14 @@ _SIGS = {
                            C.POINTER(_vp), _i, _i, _i, _l, _vp], _i),
     "fisdf_eri_fft_plan": ([_i, _i, _i, _i, _i, _l, _l, _ip, _ip, _ip, _ip, _ip, _ip, _ip,
                             C.POINTER(_l)], _i),
+    # GTH pseudopotential and nuclear-attraction matrices (atom tables: arrays of PPAtom, as _vp)
+    "fisdf_pp_nproj": ([_vp, _i], _i),
+    "fisdf_vloc_g": ([_vp, _ip, _dp, _vp, _i, _vp], _i),
+    "fisdf_gth_projectors": ([_vp, _ip, _dp, _dp, _vp, _i, _i, _i, _vp], _i),
+    "fisdf_pp_overlap": ([_vp, _vp, _i, _vp, _i, _ip, _dp, _d, _vp], _i),
+    "fisdf_get_pp": ([_vp, _vp, _l, _i, _dp, _ip, _dp, _i, _vp, _i, _i, _l, _vp], _i),
+    "fisdf_pp_plan": ([_i, _l, _i, _i, _vp, _i, _i, _l, _ip, _ip, _ip, _ip, _ip, _ip,
+                       C.POINTER(_l)], _i),
     "fisdf_get_eri": ([_vp, _vp, _i, _i, _ip, _vp, C.POINTER(_vp), _ip, _vp], _i),
     "fisdf_zgemm": ([_vp, _i, _i, _i, _i, _i, _dp, _vp, _l, _l, _vp, _l, _l, _dp, _vp, _l, _l,
                      _i, _i], _i),
@@ -200,6 +208,13 @@ class BuildResult(C.Structure):
                 ("partner", _ip), ("d_X", _vp), ("d_x4", _vp), ("d_Wq", _vp), ("d_Ws", _vp),
                 ("time_reversal", _i), ("tr_deviation", _d), ("shard_rank", _i),
                 ("shard_size", _i), ("row0", _i), ("row1", _i), ("d_W0", _vp)]
+
+
+class PPAtom(C.Structure):
+    """struct fisdf_pp_atom (include/fisdf.h): one atom of the pseudopotential table."""
+    _fields_ = [("r", _d * 3), ("z", _d), ("rloc", _d), ("c", _d * 4), ("rl", _d * 4),
+                ("h", (_d * 9) * 4), ("nexp", _i), ("bare", _i), ("nl", _i), ("n", _i * 4),
+                ("reserved", _i)]
 
 
 # struct fisdf_comm: the caller's collectives of fisdf_build_sharded (device pointers, enqueued

@@ -89,6 +89,19 @@ BASIS = {
 
 NSPH = {0: 1, 1: 3, 2: 5, 3: 7}
 
+# symbol -> nuclear charge, H to Kr (PySCF elements.charge); "X" is PySCF's ghost atom
+_ELEMENTS = ("X H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn "
+             "Ga Ge As Se Br Kr").split()
+NUC_CHARGE = {sym: z for z, sym in enumerate(_ELEMENTS)}
+
+
+def nuclear_charge(symbol):
+    """Nuclear charge of an element symbol (H to Kr; "X": a ghost atom, 0)."""
+    try:
+        return NUC_CHARGE[symbol]
+    except KeyError:
+        raise KeyError(f"no nuclear charge for the symbol {symbol!r} (H to Kr are tabulated)")
+
 
 def _radial_norm(l, exps, coefs):
     """Normalise the contracted radial part  sum_i c_i r^l exp(-a_i r^2)."""
@@ -137,14 +150,22 @@ class Cell:
     shells: list = field(default_factory=list, init=False)
     dimension: int = 3
     low_dim_ft_type: str = None
+    # GTH pseudopotentials by symbol in PySCF's ``cell._pseudo`` format, [nelec_per_l, rloc, nexp,
+    # [c1..c_nexp], nproj_types, [r_0, n_0, h_0], [r_1, n_1, h_1], ...]; a symbol without an entry
+    # is a bare nucleus.  Kept as ``_pseudo`` (fisdf.pp reads it; ISDF.get_pp)
+    pseudo: dict = field(default_factory=dict)
 
     def __post_init__(self):
         self.a = np.asarray(self.a, dtype=float).reshape(3, 3)
         self.mesh = tuple(int(m) for m in self.mesh)
+        self._pseudo = dict(self.pseudo or {})
         self.shells = []
         ao = 0
         for ia, (sym, _) in enumerate(self.atoms):
-            for (l, exps, coefs) in BASIS[(sym, self.basis)]:
+            # the toy basis is one s and one p primitive on any symbol
+            key = (sym, self.basis) if (sym, self.basis) in BASIS or self.basis != "toy" \
+                else ("X", "toy")
+            for (l, exps, coefs) in BASIS[key]:
                 c = _radial_norm(l, exps, coefs)
                 self.shells.append((ia, l, np.asarray(exps, float), c, ao))
                 ao += NSPH[l]
@@ -170,6 +191,15 @@ class Cell:
 
     def atom_coords(self):
         return np.asarray([xyz for _, xyz in self.atoms], float)
+
+    def atom_symbol(self, ia):
+        return self.atoms[ia][0]
+
+    def atom_charges(self):
+        """``Cell.atom_charges()`` [pyscf]: the ionic charge sum(nelec_per_l) of an atom whose
+        symbol has a pseudopotential, the nuclear charge otherwise."""
+        return np.asarray([sum(self._pseudo[sym][0]) if sym in self._pseudo
+                           else nuclear_charge(sym) for sym, _ in self.atoms], dtype=int)
 
     def get_kpts(self, kmesh):
         return make_kpts(self, kmesh)

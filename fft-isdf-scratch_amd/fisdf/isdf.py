@@ -534,6 +534,22 @@ class InterpolativeSeparableDensityFitting:
         nd = np.ndim(dm)
         return out[0] if nd < 4 else out
 
+    def get_pp(self, kpts=None):
+        """``FFTDF.get_pp(kpts)`` [pyscf]: the GTH pseudopotential matrices V^loc + V^nl of
+        ``cell._pseudo`` (an atom without an entry: a bare nucleus) at ``kpts`` — None: this
+        object's k-mesh; a (3,) k-point: (nao, nao); (n, 3): (n, nao, nao).  The local part is
+        the structure-factor sum in G space, one FFT and the AO Gram weighted by Re v(r); the
+        non-local part the separable GTH projectors (fisdf_get_pp).  k-points of
+        the mesh use the resident Bloch AOs, others the band AOs on the FFT grid.  No build()
+        needed.  What ``KRHF.get_hcore`` calls for a cell with ``pseudo``."""
+        return _get_pp(self, kpts, nuc=False)
+
+    def get_nuc(self, kpts=None):
+        """``FFTDF.get_nuc(kpts)`` [pyscf]: the nuclear attraction of the bare charges
+        ``cell.atom_charges()`` — get_pp's local part with every atom a bare nucleus (the G = 0
+        term dropped).  Arguments and shapes as ``get_pp``."""
+        return _get_pp(self, kpts, nuc=True)
+
     def madelung(self):
         """``tools.pbc.madelung(cell, kpts)`` [pyscf] for this k-mesh (host scalar, cached)."""
         if getattr(self, "_madelung", None) is None:
@@ -1186,6 +1202,57 @@ def _band_grid_aos(df_obj, coords, kb):
         from .ao import eval_ao_band_gpu
         return eval_ao_band_gpu(df_obj.device, cell, coords, kb)
     return df_obj.device.to_dev(bloch_ao(cell, coords, kb))   # a PySCF-protocol cell
+
+
+def _get_pp(df_obj, kpts, nuc):
+    """get_pp / get_nuc on the device (fisdf_get_pp): (n, nao, nao) on the host, or (nao, nao) for
+    a (3,) k-point.  k-points that are all points of the k-mesh take the resident Bloch AOs (the
+    whole mesh in place, a subset gathered); otherwise every point's AOs are evaluated on the FFT
+    grid, a block of points at a time."""
+    from .pp import pack_atoms
+    d = df_obj.device
+    if d.sharded(df_obj):
+        raise NotImplementedError(("get_nuc" if nuc else "get_pp") + " on a k-sharded object")
+    df_obj._kmesh()
+    cell = df_obj.cell
+    single = kpts is not None and np.ndim(kpts) == 1
+    kp = df_obj.kpts if kpts is None else np.asarray(kpts, float).reshape(-1, 3)
+    tab = pack_atoms(cell, bare=nuc)
+    natm = len(tab)
+    a = np.asarray(cell.lattice_vectors(), float)
+    mesh_c, mesh_p = _lib.iarr(df_obj.mesh)
+    a_c, a_p = _lib.darr(a.ravel())
+    nao = cell.nao_nr()
+    ngrid = int(np.prod(df_obj.mesh))
+    idx = None
+    try:
+        idx, _ = df_obj._kidx(kp)
+        if abs(np.asarray(df_obj.kpts)[idx] - kp).max() > 1e-9:
+            idx = None      # a mesh point shifted by a reciprocal vector: other k + G
+    except ValueError:
+        idx = None
+
+    def run(f, ks):
+        ks_c, ks_p = _lib.darr(ks.ravel())
+        out = d.empty((len(ks), nao, nao))
+        d.ctx.call("fisdf_get_pp", _lib.ptr(f), ngrid * nao, len(ks), ks_p, mesh_p, a_p, nao,
+                   tab, natm, 0 if nuc else 1, 0, _lib.ptr(out))
+        return d.to_host(out)
+
+    if idx is not None:
+        f = df_obj._grid_aos()
+        if not (len(idx) == f.shape[0] and np.array_equal(idx, np.arange(f.shape[0]))):
+            f = f[d.torch.as_tensor(idx.astype(np.int64), device=f.device)].contiguous()
+        v = run(f, kp)
+    else:
+        blk = max(1, int(BAND_BLOCK_BYTES // (16 * ngrid * nao)))
+        coords = df_obj.grids_coords()
+        v = np.empty((len(kp), nao, nao), complex)
+        for b0 in range(0, len(kp), blk):
+            fb = _band_grid_aos(df_obj, coords, kp[b0:b0 + blk])
+            v[b0:b0 + blk] = run(fb, kp[b0:b0 + blk])
+            del fb
+    return v[0] if single else v
 
 
 def _k_factors(df_obj, dm, ddms):

@@ -678,6 +678,77 @@ int fisdf_eri_fft_plan(int n1, int n2, int n3, int n4, int npair, long ngrid, lo
                        int* h_mc, int* h_nrow_chunks, int* h_bc, int* h_nb_chunks, int* h_b_once,
                        int* h_tw, int* h_ksplit, long* h_bytes);
 
+/* ---- GTH pseudopotential and nuclear-attraction matrices (PySCF FFTDF.get_pp / get_nuc) ----------
+ * With Omega the cell volume, N = ngrid, G the vectors of the mesh (fftfreq wrap), r_g the grid
+ * points, f_k the Bloch AOs on the grid and SI_a(G) = exp(-i G.R_a):
+ *   V_G = sum_a SI_a(G) v_a(|G|),  x = |G| rloc,
+ *   v_a(G != 0) = -Z_a (4 pi / G^2) e^{-x^2/2} + (2 pi)^{3/2} rloc^3 e^{-x^2/2}
+ *                 [c1 + c2 (3 - x^2) + c3 (15 - 10 x^2 + x^4) + c4 (105 - 105 x^2 + 21 x^4 - x^6)]
+ *   v_a(G = 0)  = 2 pi Z_a rloc^2 + (2 pi)^{3/2} rloc^3 (c1 + 3 c2 + 15 c3 + 105 c4)
+ *   (a bare nucleus: -Z_a 4 pi / G^2, and 0 at G = 0: the formulas above at rloc = 0)
+ *   v(r_g) = (1/Omega) sum_G V_G e^{i G.r_g}
+ *   Vloc_k[m,n] = (Omega/N) sum_g conj(f_k[g,m]) Re v(r_g) f_k[g,n]
+ * and, for the projector p = (a, l, i, mm), i < n_l, K = k + G, x = |K| r_l:
+ *   beta_p(G; k) = e^{-i K.R_a} P_i^l(|K|) S_{l,mm}(K)
+ *   P_i^l(K) = q_{l,i}(x) pi^{5/4} r_l^{l + 3/2} e^{-x^2/2}   (q: the table of DESIGN 3.13)
+ *   S_{l,mm}: the real solid harmonics |K|^l Y_{l,mm} of fisdf_eval_ao
+ *   c[p,m] = sum_G conj(beta_p(G; k)) (1/N) sum_g e^{-i K.r_g} f_k[g,m]
+ *   Vnl_k[m,n] = sum_{a,l,mm} sum_{ij} conj(c[(a,l,i,mm),m]) h_l[i,j] c[(a,l,j,mm),n]
+ * c is formed as sum_g t_p(r_g) e^{-i k.r_g} f_k[g,m] with t_p = (1/N) fft3d(conj beta_p): the
+ * projector rows are transformed, the AOs are read where they lie.  No atomics: repeated calls
+ * agree bit for bit, and fisdf_get_pp's result does not depend on work_bytes.
+ *
+ * One atom of the table.  A bare nucleus (bare != 0) has charge z and nothing else is read. */
+typedef struct fisdf_pp_atom {
+  double r[3];      /* position, bohr */
+  double z;         /* Z_ion of the pseudopotential, or the nuclear charge */
+  double rloc;
+  double c[4];      /* c1..c4, the first nexp are read */
+  double rl[4];     /* r_l of channel l */
+  double h[4][9];   /* h_l, row-major 3 x 3, the leading n[l] x n[l] block is read */
+  int nexp;         /* <= 4 */
+  int bare;
+  int nl;           /* angular-momentum channels l = 0..nl-1, <= 4 */
+  int n[4];         /* projectors of channel l, <= 3 (0: none) */
+  int reserved;
+} fisdf_pp_atom;
+/* projector rows of the table: sum over atoms and channels of n[l] (2 l + 1); a bare atom has
+ * none.  A negative value: the table is refused (nl > 4, n[l] > 3, nexp > 4 or a negative count,
+ * rloc <= 0 or r_l <= 0 where read) */
+int fisdf_pp_nproj(const fisdf_pp_atom* h_atoms, int natm);
+/* d_vg[G] = V_G over the mesh (ngrid c128) */
+int fisdf_vloc_g(fisdf_ctx* ctx, const int mesh[3], const double a[9],
+                 const fisdf_pp_atom* h_atoms, int natm, void* d_vg);
+/* d_rows[p][G] = conj(beta_p(G; k)) for the projectors of atoms [a0, a1) at the k-point h_k
+ * (Cartesian, 1/bohr): rows in table order (atom, l, i, mm), each of ngrid */
+int fisdf_gth_projectors(fisdf_ctx* ctx, const int mesh[3], const double a[9], const double h_k[3],
+                         const fisdf_pp_atom* h_atoms, int natm, int a0, int a1, void* d_rows);
+/* d_c[p][m] = scale sum_g d_t[p][g] exp(-i frac(g).h_kd) d_f[g][m]: d_t (np, ngrid), d_f (ngrid,
+ * nao), d_c (np, nao); frac the fftfreq fractions of the point's mesh indices (h_kd NULL: no
+ * phase), formed in the kernel.  The grid is split into runs (fisdf_pp_plan) whose partial blocks
+ * are summed in run order; the runs depend on ngrid alone */
+int fisdf_pp_overlap(fisdf_ctx* ctx, const void* d_t, int np, const void* d_f, int nao,
+                     const int mesh[3], const double* h_kd /*3 or NULL*/, double scale, void* d_c);
+/* d_out[k] (nao, nao) = Vloc_k (+ Vnl_k when with_nonlocal) for the nk k-points h_kpts (nk x 3,
+ * Cartesian, 1/bohr) whose AOs on the grid are d_f (nk, ngrid, nao) with k stride f_kstride.
+ * get_nuc is this with a table of bare nuclei and with_nonlocal = 0.  At a k-point with
+ * sum |k_d| < 1e-9 the imaginary part is set to zero.  work_bytes: the byte budget of one
+ * k-point's projector rows, 0 = the default (512 MiB); rows beyond it are taken in chunks of whole
+ * atoms, and an atom whose own rows exceed it is an error.  Every check of the table, the sizes
+ * and the mesh (the FFT's own rule included) comes before the first launch: a refused call leaves
+ * d_out untouched.  Workspace: the context's arena (fisdf_pp_plan's bytes).  Asynchronous. */
+int fisdf_get_pp(fisdf_ctx* ctx, const void* d_f, long f_kstride, int nk, const double* h_kpts,
+                 const int mesh[3], const double a[9], int nao, const fisdf_pp_atom* h_atoms,
+                 int natm, int with_nonlocal, long work_bytes, void* d_out);
+/* what fisdf_pp_overlap and fisdf_get_pp do for given sizes (host only, no context): the grid runs
+ * of the overlap (points per run, runs), its AO tiles (of 32) and, for np projector rows, its
+ * projector tiles (of 16); the atom chunks of the table under work_bytes (0: no projectors, or an
+ * atom beyond the budget; a refused table is an error) and the most rows of a chunk; the arena bytes of fisdf_get_pp with nk
+ * k-points.  h_atoms may be NULL (natm 0): no chunks, np as given.  Any output may be NULL */
+int fisdf_pp_plan(int nao, long ngrid, int nk, int np, const fisdf_pp_atom* h_atoms, int natm,
+                  int with_nonlocal, long work_bytes, int* h_run_len, int* h_nrun, int* h_mtiles,
+                  int* h_ptiles, int* h_nchunk, int* h_chunk_rows, long* h_bytes);
+
 /* ---- ISDF 4-index integrals (get_eri / ao2mo surface) --------------------------
  * eri[i*n2+j][k*n4+l] = sum_IJ W_q[I,J] conj(A1[I,i]) A2[I,j] conj(A3[J,k]) A4[J,l] with
  * A_s = X_{kidx[s]} C_s, q = k2 - k1 (fftdf-with-k-lstsq.py:221-232).  d_Wq: the (nip,nip)
