@@ -156,6 +156,7 @@ int eval_ao(hipStream_t s, const double* d_coords, int ng, int natm, const doubl
   for (int i = 0; i < nsh; ++i) {
     FISDF_CHECK(h_sh_l[i] >= 0 && h_sh_l[i] <= 3, "eval_ao: angular momentum must be <= 3");
     FISDF_CHECK(h_sh_atom[i] >= 0 && h_sh_atom[i] < natm, "eval_ao: shell atom out of range");
+    FISDF_CHECK(h_sh_nprim[i] >= 1, "eval_ao: a shell needs at least one primitive");
     sh[i] = AoShell{h_sh_atom[i], h_sh_l[i], h_sh_nprim[i], p0};
     p0 += h_sh_nprim[i];
     for (int m = 0; m < 2 * h_sh_l[i] + 1; ++m) {

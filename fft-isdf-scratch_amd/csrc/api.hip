@@ -1834,6 +1834,7 @@ int fisdf_eval_ao(fisdf_ctx* c, const void* d_coords, int ng, int natm, const do
                   const int* kmesh, const double* a, double rcut, int nao, void* d_out) {
   FISDF_TRY(device_guard(c));
   FISDF_CHECK(kmesh && kmesh[0] > 0 && kmesh[1] > 0 && kmesh[2] > 0, "eval_ao: bad k-mesh");
+  FISDF_CHECK(ng >= 0 && nT >= 0, "eval_ao: bad sizes");  // before they size the workspace
   StageTimer tm(c, FISDF_ST_AO);
   int nao_sh = 0;
   for (int i = 0; i < nsh; ++i) nao_sh += 2 * h_sh_l[i] + 1;
@@ -1861,6 +1862,7 @@ int fisdf_eval_ao_band(fisdf_ctx* c, const void* d_coords, int ng, int natm, con
                        void* d_out) {
   FISDF_TRY(device_guard(c));
   FISDF_CHECK(nkb > 0 && h_kpts != nullptr, "eval_ao_band: no band k-points");
+  FISDF_CHECK(ng >= 0 && nT >= 0, "eval_ao_band: bad sizes");  // before they size the workspace
   StageTimer tm(c, FISDF_ST_AO);
   int nao_sh = 0;
   for (int i = 0; i < nsh; ++i) nao_sh += 2 * h_sh_l[i] + 1;

@@ -52,18 +52,7 @@ def eval_ao_kpts_gpu(device, cell, coords, kmesh):
     nk = int(np.prod(kmesh))
     nao = cell.nao_nr()
     tn = np.ascontiguousarray(lattice_translations(cell, coords), dtype=np.int32)
-    sh_atom, sh_l, sh_np, exps, coefs = [], [], [], [], []
-    for (ia, l, e, c, _ao0) in cell.shells:
-        sh_atom.append(ia)
-        sh_l.append(l)
-        sh_np.append(len(e))
-        exps.extend(np.asarray(e, float).tolist())
-        coefs.extend(np.asarray(c, float).tolist())
-    sh_atom = np.asarray(sh_atom, np.int32)
-    sh_l = np.asarray(sh_l, np.int32)
-    sh_np = np.asarray(sh_np, np.int32)
-    exps = np.asarray(exps, np.float64)
-    coefs = np.asarray(coefs, np.float64)
+    sh_atom, sh_l, sh_np, exps, coefs = _shell_tables(cell)
     atoms = np.ascontiguousarray(cell.atom_coords(), dtype=np.float64)
     torch = device.torch
     dcoords = torch.as_tensor(coords, device=device.dev)

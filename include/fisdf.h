@@ -256,7 +256,10 @@ int fisdf_set_allocator(fisdf_ctx* ctx, fisdf_alloc_fn alloc, fisdf_free_fn rele
  * d_coords (ng, 3) f64 device; h_atoms (natm, 3); shells: atom, l, nprim, then the nprim
  * exponents / normalised coefficients of each shell in order; h_tn (nT, 3) the lattice
  * translations n to sum (T = n @ a, image R = n mod kmesh); terms with |r - T - atom| >= rcut
- * are dropped.  d_out (nk, ng, nao) c128, nk = prod(kmesh), kpts = make_kpts order. */
+ * are dropped.  d_out (nk, ng, nao) c128, nk = prod(kmesh), kpts = make_kpts order.  nT = 0 gives
+ * zeros, ng = 0 writes nothing.  Refused on the host, before anything is copied or launched and
+ * with d_out untouched: ng or nT < 0, l outside 0..3, a shell atom outside [0, natm), nprim < 1,
+ * nao other than sum (2 l + 1), a k-mesh axis < 1 (band entry: nkb < 1 or h_kpts NULL). */
 int fisdf_eval_ao(fisdf_ctx* ctx, const void* d_coords, int ng, int natm, const double* h_atoms,
                   int nsh, const int* h_sh_atom, const int* h_sh_l, const int* h_sh_nprim,
                   const double* h_exps, const double* h_coefs, int nT, const int* h_tn,
