@@ -51,6 +51,55 @@ __global__ __launch_bounds__(256) void ao_folded_kernel(
   }
 }
 
+// The value and the three first derivatives, F4[R][c][g][nu] (c = 0: the value, 1..3: d/dx, d/dy,
+// d/dz): d_c [R(r^2) S(d)] = R' 2 d_c S + R d_c S with R' = -sum_p alpha_p c_p exp(-alpha_p r^2).
+// One exponential per primitive serves all four components; the value is accumulated by the
+// statements of ao_folded_kernel in the same order, so component 0 has that kernel's bits.
+__global__ __launch_bounds__(256) void ao_folded_deriv1_kernel(
+    const double* __restrict__ coords, int ng, int nao, const int* __restrict__ ao_shell,
+    const int* __restrict__ ao_m, const AoShell* __restrict__ sh, const double* __restrict__ pexp,
+    const double* __restrict__ pcoef, const double* __restrict__ atoms,
+    const double* __restrict__ Tvec, const int* __restrict__ Toff, int nimg, double rc2,
+    double* __restrict__ F) {
+  const long e = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (e >= (long)ng * nao) return;
+  const int g = (int)(e / nao), nu = (int)(e % nao);
+  const AoShell s = sh[ao_shell[nu]];
+  const int m = ao_m[nu];
+  const double gx = coords[3L * g] - atoms[3 * s.atom];
+  const double gy = coords[3L * g + 1] - atoms[3 * s.atom + 1];
+  const double gz = coords[3L * g + 2] - atoms[3 * s.atom + 2];
+  const long cs = (long)ng * nao;  // component stride
+  for (int R = 0; R < nimg; ++R) {
+    double acc = 0.0, ax = 0.0, ay = 0.0, az = 0.0;
+    for (int t = Toff[R]; t < Toff[R + 1]; ++t) {
+      const double dx = gx - Tvec[3 * t], dy = gy - Tvec[3 * t + 1], dz = gz - Tvec[3 * t + 2];
+      const double r2 = dx * dx + dy * dy + dz * dz;
+      if (r2 < rc2) {
+        double rad = 0.0, drad = 0.0;  // R and 2 R'
+        for (int p = 0; p < s.nprim; ++p) {
+          const double ex = exp(-pexp[s.p0 + p] * r2);
+          rad += ex * pcoef[s.p0 + p];
+          drad += ex * (-2.0 * pexp[s.p0 + p] * pcoef[s.p0 + p]);
+        }
+        const double S = real_sph(s.l, m, dx, dy, dz);
+        double sx, sy, sz;
+        real_sph_grad(s.l, m, dx, dy, dz, sx, sy, sz);
+        acc += rad * S;
+        const double dS = drad * S;
+        ax += dS * dx + rad * sx;
+        ay += dS * dy + rad * sy;
+        az += dS * dz + rad * sz;
+      }
+    }
+    double* o = F + (long)R * 4 * cs + (long)g * nao + nu;
+    o[0] = acc;
+    o[cs] = ax;
+    o[2 * cs] = ay;
+    o[3 * cs] = az;
+  }
+}
+
 template <int N, int S, int NK>
 __device__ __forceinline__ void ao_axis_dft(cplx* v, const cplx* tw) {
 #pragma unroll
@@ -144,8 +193,9 @@ int eval_ao(hipStream_t s, const double* d_coords, int ng, int natm, const doubl
             const int* h_sh_atom, const int* h_sh_l, const int* h_sh_nprim, const double* h_exps,
             const double* h_coefs, int nT, const int* h_tn, const int kmesh[3], const double a[9],
             double rcut, double* F, void* scratch, size_t scratch_size, cplx* chi, int* h_nao,
-            int nkb, const double* h_kband) {
+            int nkb, const double* h_kband, int deriv) {
   FISDF_CHECK(ng >= 0 && natm > 0 && nsh > 0 && nT >= 0, "eval_ao: bad sizes");
+  FISDF_CHECK(deriv == 0 || deriv == 1, "eval_ao: deriv must be 0 or 1");
   // band mode (nkb > 0): every translation is its own image, phases exp(i k.T) per band k
   const bool band = nkb > 0;
   const int nimg = band ? std::max(nT, 1) : kmesh[0] * kmesh[1] * kmesh[2];
@@ -224,7 +274,10 @@ int eval_ao(hipStream_t s, const double* d_coords, int ng, int natm, const doubl
     return 0;
   }
   const long nth = (long)ng * nao;
-  hipLaunchKernelGGL(ao_folded_kernel, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, s,
+  // deriv = 1: F holds (nimg, 4, ng, nao), and the four components pass the transforms below as
+  // 4 ng nao columns
+  hipLaunchKernelGGL(deriv ? ao_folded_deriv1_kernel : ao_folded_kernel,
+                     dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, s,
                      d_coords, ng, nao, (const int*)(b + oAS), (const int*)(b + oAM),
                      (const AoShell*)(b + oS), (const double*)(b + oE), (const double*)(b + oC),
                      (const double*)(b + oA), (const double*)(b + oT), (const int*)(b + oO), nimg,
@@ -232,7 +285,7 @@ int eval_ao(hipStream_t s, const double* d_coords, int ng, int natm, const doubl
   FISDF_HIP(hipGetLastError());
   // the host tables must outlive the asynchronous copies
   FISDF_HIP(hipStreamSynchronize(s));
-  const long ncol = nth;
+  const long ncol = deriv ? 4 * nth : nth;
   if (band) return bloch_band(s, F, ncol, nT, (const cplx*)(b + oP), nkb, chi);
   return bloch_dft(s, F, ncol, kmesh, chi);
 }

@@ -1828,10 +1828,13 @@ int fisdf_unpack_slices(fisdf_ctx* c, const void* recv, int nrows, int nparts, c
 }
 
 // ---- input layer: Bloch AO values -------------------------------------
-int fisdf_eval_ao(fisdf_ctx* c, const void* d_coords, int ng, int natm, const double* h_atoms,
+namespace {
+
+// fisdf_eval_ao / fisdf_eval_ao_deriv1: ncomp = 1 values, 4 values and first derivatives
+int eval_ao_entry(fisdf_ctx* c, const void* d_coords, int ng, int natm, const double* h_atoms,
                   int nsh, const int* h_sh_atom, const int* h_sh_l, const int* h_sh_nprim,
                   const double* h_exps, const double* h_coefs, int nT, const int* h_tn,
-                  const int* kmesh, const double* a, double rcut, int nao, void* d_out) {
+                  const int* kmesh, const double* a, double rcut, int nao, void* d_out, int deriv) {
   FISDF_TRY(device_guard(c));
   FISDF_CHECK(kmesh && kmesh[0] > 0 && kmesh[1] > 0 && kmesh[2] > 0, "eval_ao: bad k-mesh");
   FISDF_CHECK(ng >= 0 && nT >= 0, "eval_ao: bad sizes");  // before they size the workspace
@@ -1840,8 +1843,9 @@ int fisdf_eval_ao(fisdf_ctx* c, const void* d_coords, int ng, int natm, const do
   for (int i = 0; i < nsh; ++i) nao_sh += 2 * h_sh_l[i] + 1;
   FISDF_CHECK(nao_sh == nao, "eval_ao: nao does not match the shells");
   const int nimg = kmesh[0] * kmesh[1] * kmesh[2];
+  const size_t ncomp = deriv ? 4 : 1;
   Carver cv;
-  const size_t oF = cv.take(sizeof(double) * (size_t)nimg * ng * nao);
+  const size_t oF = cv.take(sizeof(double) * ncomp * (size_t)nimg * ng * nao);
   const size_t tables = 1 << 20;
   const size_t oT = cv.take(tables + sizeof(double) * 3 * (size_t)std::max(nT, 1));
   void* base;
@@ -1851,15 +1855,15 @@ int fisdf_eval_ao(fisdf_ctx* c, const void* d_coords, int ng, int natm, const do
   FISDF_TRY(eval_ao(c->stream, (const double*)d_coords, ng, natm, h_atoms, nsh, h_sh_atom,
                     h_sh_l, h_sh_nprim, h_exps, h_coefs, nT, h_tn, kmesh, a, rcut,
                     (double*)(b + oF), b + oT, tables + sizeof(double) * 3 * (size_t)std::max(nT, 1),
-                    (cplx*)d_out, &nao_out));
+                    (cplx*)d_out, &nao_out, 0, nullptr, deriv));
   return 0;
 }
 
-int fisdf_eval_ao_band(fisdf_ctx* c, const void* d_coords, int ng, int natm, const double* h_atoms,
+int eval_ao_band_entry(fisdf_ctx* c, const void* d_coords, int ng, int natm, const double* h_atoms,
                        int nsh, const int* h_sh_atom, const int* h_sh_l, const int* h_sh_nprim,
                        const double* h_exps, const double* h_coefs, int nT, const int* h_tn,
                        int nkb, const double* h_kpts, const double* a, double rcut, int nao,
-                       void* d_out) {
+                       void* d_out, int deriv) {
   FISDF_TRY(device_guard(c));
   FISDF_CHECK(nkb > 0 && h_kpts != nullptr, "eval_ao_band: no band k-points");
   FISDF_CHECK(ng >= 0 && nT >= 0, "eval_ao_band: bad sizes");  // before they size the workspace
@@ -1868,8 +1872,9 @@ int fisdf_eval_ao_band(fisdf_ctx* c, const void* d_coords, int ng, int natm, con
   for (int i = 0; i < nsh; ++i) nao_sh += 2 * h_sh_l[i] + 1;
   FISDF_CHECK(nao_sh == nao, "eval_ao_band: nao does not match the shells");
   const int one[3] = {1, 1, 1};
+  const size_t ncomp = deriv ? 4 : 1;
   Carver cv;
-  const size_t oF = cv.take(sizeof(double) * (size_t)std::max(nT, 1) * ng * nao);
+  const size_t oF = cv.take(sizeof(double) * ncomp * (size_t)std::max(nT, 1) * ng * nao);
   const size_t tables = (1 << 20) + sizeof(double) * 3 * (size_t)std::max(nT, 1) +
                         sizeof(cplx) * (size_t)std::max(nT, 1) * nkb + sizeof(int) * (nT + 2);
   const size_t oT = cv.take(tables);
@@ -1879,8 +1884,47 @@ int fisdf_eval_ao_band(fisdf_ctx* c, const void* d_coords, int ng, int natm, con
   int nao_out = 0;
   FISDF_TRY(eval_ao(c->stream, (const double*)d_coords, ng, natm, h_atoms, nsh, h_sh_atom, h_sh_l,
                     h_sh_nprim, h_exps, h_coefs, nT, h_tn, one, a, rcut, (double*)(b + oF), b + oT,
-                    tables, (cplx*)d_out, &nao_out, nkb, h_kpts));
+                    tables, (cplx*)d_out, &nao_out, nkb, h_kpts, deriv));
   return 0;
+}
+
+}  // namespace
+
+int fisdf_eval_ao(fisdf_ctx* c, const void* d_coords, int ng, int natm, const double* h_atoms,
+                  int nsh, const int* h_sh_atom, const int* h_sh_l, const int* h_sh_nprim,
+                  const double* h_exps, const double* h_coefs, int nT, const int* h_tn,
+                  const int* kmesh, const double* a, double rcut, int nao, void* d_out) {
+  return eval_ao_entry(c, d_coords, ng, natm, h_atoms, nsh, h_sh_atom, h_sh_l, h_sh_nprim, h_exps,
+                       h_coefs, nT, h_tn, kmesh, a, rcut, nao, d_out, 0);
+}
+
+int fisdf_eval_ao_band(fisdf_ctx* c, const void* d_coords, int ng, int natm, const double* h_atoms,
+                       int nsh, const int* h_sh_atom, const int* h_sh_l, const int* h_sh_nprim,
+                       const double* h_exps, const double* h_coefs, int nT, const int* h_tn,
+                       int nkb, const double* h_kpts, const double* a, double rcut, int nao,
+                       void* d_out) {
+  return eval_ao_band_entry(c, d_coords, ng, natm, h_atoms, nsh, h_sh_atom, h_sh_l, h_sh_nprim,
+                            h_exps, h_coefs, nT, h_tn, nkb, h_kpts, a, rcut, nao, d_out, 0);
+}
+
+// ---- AO first derivatives: d_out (nk, 4, ng, nao) ---------------------------
+int fisdf_eval_ao_deriv1(fisdf_ctx* c, const void* d_coords, int ng, int natm,
+                         const double* h_atoms, int nsh, const int* h_sh_atom, const int* h_sh_l,
+                         const int* h_sh_nprim, const double* h_exps, const double* h_coefs, int nT,
+                         const int* h_tn, const int* kmesh, const double* a, double rcut, int nao,
+                         void* d_out) {
+  return eval_ao_entry(c, d_coords, ng, natm, h_atoms, nsh, h_sh_atom, h_sh_l, h_sh_nprim, h_exps,
+                       h_coefs, nT, h_tn, kmesh, a, rcut, nao, d_out, 1);
+}
+
+int fisdf_eval_ao_band_deriv1(fisdf_ctx* c, const void* d_coords, int ng, int natm,
+                              const double* h_atoms, int nsh, const int* h_sh_atom,
+                              const int* h_sh_l, const int* h_sh_nprim, const double* h_exps,
+                              const double* h_coefs, int nT, const int* h_tn, int nkb,
+                              const double* h_kpts, const double* a, double rcut, int nao,
+                              void* d_out) {
+  return eval_ao_band_entry(c, d_coords, ng, natm, h_atoms, nsh, h_sh_atom, h_sh_l, h_sh_nprim,
+                            h_exps, h_coefs, nT, h_tn, nkb, h_kpts, a, rcut, nao, d_out, 1);
 }
 
 int fisdf_gather_points(fisdf_ctx* c, const void* x0, int nk, int ng0, int nao, const int* h_perm,
@@ -3603,6 +3647,34 @@ int fisdf_get_rho(fisdf_ctx* c, const void* fv, long f_kstride, int nk, int ngri
   StageTimer tm(c, FISDF_ST_J);
   return rho_grid(c->stream, (const cplx*)fv, f_kstride, nk, ngrid, nao, (const cplx*)dmsv, nset,
                   (cplx*)rhov);
+}
+
+int fisdf_get_rho_gga(fisdf_ctx* c, const void* f4v, long f_kstride, long f_cstride, int nk, int ng,
+                      int nao, const void* dmsv, int nset, int hermi, void* rhov,
+                      long rho_cstride) {
+  FISDF_TRY(device_guard(c));
+  StageTimer tm(c, FISDF_ST_J);
+  return rho_grid_gga(c->stream, (const cplx*)f4v, f_kstride, f_cstride, nk, ng, nao,
+                      (const cplx*)dmsv, nset, hermi, (cplx*)rhov, rho_cstride);
+}
+
+int fisdf_gga_gram(fisdf_ctx* c, const void* f4v, long f_kstride, long f_cstride, int nk, int ng,
+                   int nao, const void* wv, long w_sstride, long w_cstride, int nset, double scale,
+                   int accumulate, void* outv) {
+  FISDF_TRY(device_guard(c));
+  FISDF_CHECK(nk >= 1 && ng >= 1 && nao >= 1 && nset >= 1, "gga_gram: sizes must be >= 1");
+  StageTimer tm(c, FISDF_ST_J);
+  size_t na, nm, ns;
+  gga_gram_work(nk, ng, nao, &na, &nm, &ns);
+  Carver cv;
+  const size_t oA = cv.take(sizeof(cplx) * na), oM = cv.take(sizeof(cplx) * nm),
+               oS = cv.take(sizeof(cplx) * ns);
+  void* base;
+  FISDF_TRY(arena_get(c, cv.off, &base));
+  char* b = (char*)base;
+  return gga_gram(c->stream, (const cplx*)f4v, f_kstride, f_cstride, nk, ng, nao,
+                  (const double*)wv, w_sstride, w_cstride, nset, scale, accumulate, (cplx*)outv,
+                  (cplx*)(b + oA), (cplx*)(b + oM), ns ? (cplx*)(b + oS) : nullptr);
 }
 
 int fisdf_coulomb_potential(fisdf_ctx* c, const void* rhov, int nset, const int mesh[3],

@@ -131,7 +131,7 @@ int eval_ao(hipStream_t s, const double* d_coords, int ng, int natm, const doubl
             const int* h_sh_atom, const int* h_sh_l, const int* h_sh_nprim, const double* h_exps,
             const double* h_coefs, int nT, const int* h_tn, const int kmesh[3], const double a[9],
             double rcut, double* F, void* scratch, size_t scratch_size, cplx* chi, int* h_nao,
-            int nkb = 0, const double* h_kband = nullptr);
+            int nkb = 0, const double* h_kband = nullptr, int deriv = 0);
 // conj_out: store conj(y_q) — the x4 build's Phi^H x4_s (fftisdf.py:46; x4_s real) where the y
 // build has Phi^T y_s (:84)
 int kmesh_y(hipStream_t s, const cplx* FX, long ncol, const int kmesh[3], const int* h_qs,
@@ -202,6 +202,23 @@ int weighted_gram(hipStream_t s, const cplx* f, long fks, int nk, int ngrid, int
                   long work_elems);
 // a[e] = conj(a[e]): ifft(x) = conj(fft(conj(x))) / N around the forward fft3d
 int conj_inplace(hipStream_t s, cplx* a, long n);
+
+// ---- GGA density and potential matrix over the four-component AO block (xc.hip) ---------------
+// f4: component c of k-point k at f4 + k fks + c fcs, (ngrid, nao) each.
+// rho[(s 4 + c) rcs + g]: c = 0 the density of rho_grid, c = 1..3 its gradient; hermi = 1 takes
+// D Hermitian (gradient 2 Re(t conj d_c f), imaginary part exactly 0), hermi = 0 both terms.
+// rho_gga_set_chunk sets per pass over f4 (4; 2 for hermi = 0 with D tiled, nao > 32); no workspace
+int rho_grid_gga(hipStream_t s, const cplx* f4, long fks, long fcs, int nk, int ngrid, int nao,
+                 const cplx* D, int nset, int hermi, cplx* rho, long rcs);
+bool rho_gga_tiled(int nao);
+int rho_gga_set_chunk(int nao, int hermi);
+size_t rho_gga_lds_bytes(int nao, int sc, int hermi);
+// out[s][k] (+)= scale (M + M^H), M = f_k^H aow_k, aow = 1/2 w_0 f + sum_c w_c d_c f; w real,
+// w[s wss + c wcs + g].  Workspaces in complex elements from gga_gram_work (split: 0 = none)
+void gga_gram_work(int nk, int ng, int nao, size_t* aow, size_t* m, size_t* split);
+int gga_gram(hipStream_t s, const cplx* f4, long fks, long fcs, int nk, int ng, int nao,
+             const double* w, long wss, long wcs, int nset, double scale, int accumulate, cplx* out,
+             cplx* aow, cplx* M, cplx* split);
 
 // ---- exact FFT-grid K (kfft.hip; PySCF fft_jk.get_k_kpts) in its two forms: the dm form, nao
 // transform rows per row m, and the occupied-orbital (low-rank) form below ----

@@ -48,6 +48,10 @@ _SIGS = {
                        _i, _vp], _i),
     "fisdf_eval_ao_band": ([_vp, _vp, _i, _i, _dp, _i, _ip, _ip, _ip, _dp, _dp, _i, _ip, _i, _dp,
                             _dp, _d, _i, _vp], _i),
+    "fisdf_eval_ao_deriv1": ([_vp, _vp, _i, _i, _dp, _i, _ip, _ip, _ip, _dp, _dp, _i, _ip, _ip, _dp,
+                              _d, _i, _vp], _i),
+    "fisdf_eval_ao_band_deriv1": ([_vp, _vp, _i, _i, _dp, _i, _ip, _ip, _ip, _dp, _dp, _i, _ip, _i,
+                                   _dp, _dp, _d, _i, _vp], _i),
     "fisdf_get_j_band_rows": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp], _i),
     "fisdf_select_gram": ([_vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "fisdf_select_pivots": ([_vp, _vp, _i, _i, _i, _d, _ip, _ip, _ip], _i),
@@ -90,6 +94,9 @@ _SIGS = {
     "fisdf_build_ws_blocks": ([_vp, _vp, _ip, _dp, _i, _i, _ip, _dp, _i, _ip, _l, _vp], _i),
     # exact FFT-grid J and density
     "fisdf_get_rho": ([_vp, _vp, _l, _i, _i, _i, _vp, _i, _vp], _i),
+    # GGA density and potential matrix over the four-component AO block
+    "fisdf_get_rho_gga": ([_vp, _vp, _l, _l, _i, _i, _i, _vp, _i, _i, _vp, _l], _i),
+    "fisdf_gga_gram": ([_vp, _vp, _l, _l, _i, _i, _i, _vp, _l, _l, _i, _d, _i, _vp], _i),
     "fisdf_coulomb_potential": ([_vp, _vp, _i, _ip, _dp, _d, _vp], _i),
     "fisdf_weighted_gram": ([_vp, _vp, _l, _i, _i, _i, _vp, _i, _i, _d, _vp], _i),
     "fisdf_get_j_fft": ([_vp, _vp, _l, _ip, _ip, _dp, _i, _vp, _i, _d, _vp, _i, _vp], _i),

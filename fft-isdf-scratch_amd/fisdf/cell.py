@@ -138,6 +138,56 @@ def _real_sph(l, x, y, z):
     raise NotImplementedError(l)
 
 
+def _real_sph_grad(l, x, y, z):
+    """Gradients (d/dx, d/dy, d/dz) of ``_real_sph(l, ...)``'s components: polynomials of degree
+    l - 1 (no division by r)."""
+    o = np.zeros_like(x)
+    if l == 0:
+        return [(o, o, o)]
+    if l == 1:
+        c = o + 0.4886025119029199
+        return [(c, o, o), (o, c, o), (o, o, c)]
+    if l == 2:
+        c, c2, c4 = 1.0925484305920792, 0.31539156525252005, 0.5462742152960396
+        return [(c * y, c * x, o), (o, c * z, c * y), (c2 * (-2 * x), c2 * (-2 * y), c2 * (4 * z)),
+                (c * z, o, c * x), (c4 * (2 * x), c4 * (-2 * y), o)]
+    if l == 3:
+        xx, yy, zz = x * x, y * y, z * z
+        a, b, c = 0.5900435899266435, 2.890611442640554, 0.4570457994644658
+        d, e = 0.3731763325901154, 1.445305721320277
+        return [(a * (6 * x * y), a * (3 * xx - 3 * yy), o),
+                (b * (y * z), b * (x * z), b * (x * y)),
+                (c * (-2 * x * y), c * (4 * zz - xx - 3 * yy), c * (8 * y * z)),
+                (d * (-6 * x * z), d * (-6 * y * z), d * (6 * zz - 3 * xx - 3 * yy)),
+                (c * (4 * zz - 3 * xx - yy), c * (-2 * x * y), c * (8 * x * z)),
+                (e * (2 * x * z), e * (-2 * y * z), e * (xx - yy)),
+                (a * (3 * xx - 3 * yy), a * (-6 * x * y), o)]
+    raise NotImplementedError(l)
+
+
+def _shell_block(l, exps, cs, d, r2, deriv=0):
+    """One shell at the displacements d (n, 3): (n, 2l+1) values, or with deriv=1 (4, n, 2l+1):
+    the values and d_c [R(r^2) S] = R' 2 d_c S + R d_c S, R' = -sum_p alpha_p c_p e^{-alpha_p r^2}."""
+    ex = np.exp(-np.outer(r2, exps))
+    rad = ex @ cs
+    angs = _real_sph(l, d[:, 0], d[:, 1], d[:, 2])
+    val = np.stack([rad * g for g in angs], axis=1)
+    if not deriv:
+        return val
+    drad = ex @ (-2.0 * exps * cs)                       # 2 R'
+    grads = _real_sph_grad(l, d[:, 0], d[:, 1], d[:, 2])
+    out = [val]
+    for c in range(3):
+        out.append(np.stack([drad * g * d[:, c] + rad * gg[c] for g, gg in zip(angs, grads)],
+                            axis=1))
+    return np.stack(out)
+
+
+def _check_deriv(deriv):
+    if deriv not in (0, 1):
+        raise ValueError(f"deriv must be 0 or 1, not {deriv!r}")
+
+
 @dataclass
 class Cell:
     """Minimal stand-in for ``pyscf.pbc.gto.Cell`` (lengths in bohr internally)."""
@@ -213,13 +263,20 @@ class Cell:
         return cartesian_prod(rx) @ self.reciprocal_vectors()
 
     def pbc_eval_gto(self, eval_name, coords, kpts=None):
-        """``Cell.pbc_eval_gto(eval_name, coords, kpts)`` [pyscf] for AO values ('GTOval'):
-        (nk, ng, nao) complex for a (nk, 3) ``kpts``, (ng, nao) for one k-point or None — the
-        entry the reference calls for its AO inputs (fftisdf.py:367-370)."""
-        if eval_name not in ("GTOval", "GTOval_sph"):
-            raise NotImplementedError(f"pbc_eval_gto: {eval_name!r} (AO values only)")
+        """``Cell.pbc_eval_gto(eval_name, coords, kpts)`` [pyscf] for AO values ('GTOval',
+        'GTOval_sph'): (nk, ng, nao) complex for a (nk, 3) ``kpts``, (ng, nao) for one k-point or
+        None — the entry the reference calls for its AO inputs (fftisdf.py:367-370) — and for the
+        values with their first derivatives ('GTOval_deriv1', 'GTOval_sph_deriv1'): (nk, 4, ng,
+        nao), or (4, ng, nao)."""
+        if eval_name in ("GTOval", "GTOval_sph"):
+            deriv = 0
+        elif eval_name in ("GTOval_deriv1", "GTOval_sph_deriv1"):
+            deriv = 1
+        else:
+            raise NotImplementedError(f"pbc_eval_gto: {eval_name!r} (AO values and first "
+                                      "derivatives only)")
         k = np.zeros((1, 3)) if kpts is None else np.asarray(kpts, float)
-        out = eval_ao_band(self, coords, k.reshape(-1, 3))
+        out = eval_ao_band(self, coords, k.reshape(-1, 3), deriv=deriv)
         return out[0] if kpts is None or k.ndim == 1 else out
 
     def rcut(self):
@@ -237,29 +294,32 @@ def cell_rcut(cell):
     return float(r() if callable(r) else r)
 
 
-def bloch_ao(cell, coords, kpts, kmesh=None):
-    """Bloch AO values chi_k(r) (nk, ng, nao) complex128 on the host, for any cell object.
+def bloch_ao(cell, coords, kpts, kmesh=None, deriv=0):
+    """Bloch AO values chi_k(r) (nk, ng, nao) complex128 on the host, for any cell object; with
+    deriv=1 the values and their first derivatives, (nk, 4, ng, nao).
 
     * a cell of this module (explicit ``shells``): the restatement — ``eval_ao_kpts`` on the
       k-mesh grid when ``kmesh`` is given (kpts = make_kpts(cell, kmesh)), else ``eval_ao_band``;
     * any other cell with PySCF's ``pbc_eval_gto`` (a ``pyscf.pbc.gto.Cell`` or a duck-typed
       one): ``cell.pbc_eval_gto("GTOval", coords, kpts=kpts)``, exactly the reference's AO input
       (fftisdf.py:367-370; ``aoR_loop`` / ``KNumInt.block_loop``, :327-355, evaluates the same
-      values block by block)."""
+      values block by block); deriv=1 asks for ``"GTOval_sph_deriv1"``."""
+    _check_deriv(deriv)
     coords = np.asarray(coords, float)
     kpts = np.asarray(kpts, float).reshape(-1, 3)
     if hasattr(cell, "shells"):
         if kmesh is not None:
-            return eval_ao_kpts(cell, coords, kmesh)
-        return eval_ao_band(cell, coords, kpts)
+            return eval_ao_kpts(cell, coords, kmesh, deriv=deriv)
+        return eval_ao_band(cell, coords, kpts, deriv=deriv)
     if not hasattr(cell, "pbc_eval_gto"):
         raise TypeError(f"{type(cell).__name__}: a cell needs pbc_eval_gto (PySCF Cell protocol) "
                         "or explicit shells (fisdf.cell.Cell) to supply AO values")
-    ao = cell.pbc_eval_gto("GTOval", coords, kpts=kpts)
+    ao = cell.pbc_eval_gto("GTOval_sph_deriv1" if deriv else "GTOval", coords, kpts=kpts)
     ao = np.asarray(ao)
     nao = cell.nao_nr()
-    if ao.shape != (len(kpts), len(coords), nao):   # a single k-point may come back unbatched
-        ao = ao.reshape(len(kpts), len(coords), nao)
+    shape = (len(kpts), 4, len(coords), nao) if deriv else (len(kpts), len(coords), nao)
+    if ao.shape != shape:   # a single k-point may come back unbatched
+        ao = ao.reshape(shape)
     return ao.astype(np.complex128, copy=False)
 
 
@@ -305,11 +365,13 @@ def lattice_translations(cell, coords):
     return cartesian_prod([np.arange(lo[i], hi[i] + 1) for i in range(3)])
 
 
-def eval_ao_folded(cell, coords, kmesh):
-    """F_R(r) = sum_{T == T_R mod kmesh} phi(r - T), real, shape (nimg, ng, nao).
+def eval_ao_folded(cell, coords, kmesh, deriv=0):
+    """F_R(r) = sum_{T == T_R mod kmesh} phi(r - T), real, shape (nimg, ng, nao); deriv=1:
+    (nimg, 4, ng, nao), the values and their x, y, z derivatives.
 
     Bloch AOs follow as chi_k = sqrt(nk) * Phi^T F  (SURVEY A1), see ``eval_ao_kpts``.
     """
+    _check_deriv(deriv)
     coords = np.asarray(coords, float)
     ng = coords.shape[0]
     kmesh = tuple(int(k) for k in kmesh)
@@ -317,7 +379,7 @@ def eval_ao_folded(cell, coords, kmesh):
     nao = cell.nao_nr()
     a = cell.lattice_vectors()
     rc = cell_rcut(cell)
-    out = np.zeros((nimg, ng, nao))
+    out = np.zeros((nimg, 4, ng, nao) if deriv else (nimg, ng, nao))
     atom_xyz = cell.atom_coords()
     rc2 = rc * rc
     shells_by_atom = {}
@@ -337,18 +399,18 @@ def eval_ao_folded(cell, coords, kmesh):
             r2m = r2[m]
             idx = np.nonzero(m)[0]
             for (_, l, exps, cs, ao0) in shells_by_atom.get(ia, []):
-                rad = np.exp(-np.outer(r2m, exps)) @ cs
-                angs = _real_sph(l, dm[:, 0], dm[:, 1], dm[:, 2])
-                blk = np.stack([rad * g for g in angs], axis=1)
-                out[ridx, idx, ao0:ao0 + NSPH[l]] += blk
+                blk = _shell_block(l, exps, cs, dm, r2m, deriv)
+                out[ridx, ..., idx, ao0:ao0 + NSPH[l]] += blk.swapaxes(0, 1) if deriv else blk
     return out
 
 
-def eval_ao_band(cell, coords, kpts):
+def eval_ao_band(cell, coords, kpts, deriv=0):
     """Bloch AO values at arbitrary k-points (kpts_band), (nkb, ng, nao) complex128:
     chi_k(r) = sum_T exp(i k.T) phi(r - T) over the translations of ``lattice_translations``
     (pbc_eval_gto at band k-points [pyscf]; off the k-mesh the image folding of
-    ``eval_ao_folded`` does not apply)."""
+    ``eval_ao_folded`` does not apply).  deriv=1: (nkb, 4, ng, nao), the values and their x, y, z
+    derivatives."""
+    _check_deriv(deriv)
     coords = np.asarray(coords, float)
     kpts = np.asarray(kpts, float).reshape(-1, 3)
     ng = coords.shape[0]
@@ -356,14 +418,14 @@ def eval_ao_band(cell, coords, kpts):
     a = cell.lattice_vectors()
     rc2 = cell_rcut(cell) ** 2
     atom_xyz = cell.atom_coords()
-    out = np.zeros((len(kpts), ng, nao), complex)
+    out = np.zeros((len(kpts), 4, ng, nao) if deriv else (len(kpts), ng, nao), complex)
     shells_by_atom = {}
     for sh in cell.shells:
         shells_by_atom.setdefault(sh[0], []).append(sh)
     for n in lattice_translations(cell, coords):
         T = n @ a
         ph = np.exp(1j * kpts @ T)
-        F = np.zeros((ng, nao))
+        F = np.zeros((4, ng, nao) if deriv else (ng, nao))
         for ia in range(cell.natm):
             d = coords - (atom_xyz[ia] + T)
             r2 = np.einsum("gi,gi->g", d, d)
@@ -373,21 +435,21 @@ def eval_ao_band(cell, coords, kpts):
             dm = d[m]
             idx = np.nonzero(m)[0]
             for (_, l, exps, cs, ao0) in shells_by_atom.get(ia, []):
-                rad = np.exp(-np.outer(r2[m], exps)) @ cs
-                angs = _real_sph(l, dm[:, 0], dm[:, 1], dm[:, 2])
-                F[idx, ao0:ao0 + NSPH[l]] += np.stack([rad * g for g in angs], axis=1)
-        out += ph[:, None, None] * F[None]
+                blk = _shell_block(l, exps, cs, dm, r2[m], deriv)
+                F[..., idx, ao0:ao0 + NSPH[l]] += blk
+        out += ph.reshape((-1,) + (1,) * F.ndim) * F[None]
     return out
 
 
-def eval_ao_kpts(cell, coords, kmesh, folded=None):
-    """Bloch AO values chi_k(r), shape (nk, ng, nao), complex128 (pbc_eval_gto 'GTOval')."""
+def eval_ao_kpts(cell, coords, kmesh, folded=None, deriv=0):
+    """Bloch AO values chi_k(r), shape (nk, ng, nao), complex128 (pbc_eval_gto 'GTOval');
+    deriv=1: (nk, 4, ng, nao) ('GTOval_deriv1'; ``folded`` then in that layout too)."""
     if folded is None:
-        folded = eval_ao_folded(cell, coords, kmesh)
-    nimg, ng, nao = folded.shape
+        folded = eval_ao_folded(cell, coords, kmesh, deriv=deriv)
+    nimg = folded.shape[0]
     phase = get_phase(cell, kmesh)
     chi = (np.sqrt(nimg) * phase.T) @ folded.reshape(nimg, -1)
-    return chi.reshape(nimg, ng, nao)
+    return chi.reshape(folded.shape)
 
 
 # --------------------------------------------------------------------------

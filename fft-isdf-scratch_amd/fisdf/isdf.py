@@ -193,6 +193,12 @@ class InterpolativeSeparableDensityFitting:
     # build() needed, defined at any k-points that conserve momentum.
     eri_method = "isdf"
     ERI_METHODS = ("isdf", "fft")
+    # byte budget of one grid block of the AO values with their first derivatives, (nk, 4, nb, nao)
+    # complex plus the evaluator's folded workspace: get_rho(xctype="GGA"), nr_vxc_mat and get_kin
+    # walk the FFT grid in blocks of nb points (the four-component array is never resident: 5 GB
+    # at nk 64, 36^3, nao 26).  Below one point: ValueError
+    deriv_work_bytes = 512 << 20
+    XCTYPES = ("LDA", "GGA")
 
     def __init__(self, cell, kpts, m0=None, c0=20.0, device=None, comm=None):
         self.cell = cell
@@ -266,14 +272,17 @@ class InterpolativeSeparableDensityFitting:
         return build(self)
 
     def aoR_loop(self, grids=None, kpts=None, deriv=0, blksize=None):
-        """fftisdf.py:327-355: yields ((ao_k,), g0, g1) over blocks of the FFT grid (host)."""
-        assert deriv == 0
+        """fftisdf.py:327-355: yields ((ao_k,), g0, g1) over blocks of the FFT grid (host);
+        ao_k (nk, nb, nao), or with deriv=1 (nk, 4, nb, nao): the values and their x, y, z
+        derivatives (PySCF's eval_ao_kpts(..., deriv=1) layout per k-point)."""
+        if deriv not in (0, 1):
+            raise ValueError(f"aoR_loop: deriv must be 0 or 1, not {deriv!r}")
         coords = self.grids_coords() if grids is None else np.asarray(getattr(grids, "coords", grids))
         blksize = self.blksize if blksize is None else blksize
         kmesh = self._kmesh()
         for g0 in range(0, coords.shape[0], blksize):
             g1 = min(g0 + blksize, coords.shape[0])
-            yield (bloch_ao(self.cell, coords[g0:g1], self.kpts, kmesh),), g0, g1
+            yield (bloch_ao(self.cell, coords[g0:g1], self.kpts, kmesh, deriv=deriv),), g0, g1
 
     def select_interpolation_points(self, x0=None, phase=None):
         """fftisdf.py:357-388 on the GPU; returns X = x0[:, perm[:nip], :] as a host array."""
@@ -508,31 +517,75 @@ class InterpolativeSeparableDensityFitting:
             self._ao_grid = self._eval_ao(self.grids_coords())
         return self._ao_grid
 
-    def get_rho(self, dm, hermi=1):
+    def get_rho(self, dm, hermi=1, xctype="LDA"):
         """Electron density on the FFT grid, rho[g] = (1/nk) sum_k sum_mn chi_k[g,m] D_k[m,n]
         conj(chi_k[g,n]) (PySCF fft_jk.get_j_kpts' rhoR; integrates to the electron count with the
         weight vol/ngrid): (nset, ngrid), or (ngrid,) for a single dm (nk, nao, nao).  hermi=1:
         the dms are Hermitian, rho is returned real after checking max |Im| <= 1e-10 max |rho|;
-        hermi=0: complex."""
+        hermi=0: complex.
+
+        xctype="GGA": the density with its gradient, (nset, 4, ngrid) or (4, ngrid) — component 0
+        rho, 1..3 d rho / dx, dy, dz (PySCF ``eval_rho(..., xctype="GGA")``'s layout).  The AO
+        values and derivatives are evaluated a grid block at a time (``deriv_work_bytes``) and
+        consumed by fisdf_get_rho_gga; the result does not depend on the budget, bit for bit."""
+        if xctype not in self.XCTYPES:
+            raise ValueError(f"get_rho: xctype must be one of {list(self.XCTYPES)}, "
+                             f"not {xctype!r}")
         d = self.device
         if d.sharded(self):
             raise NotImplementedError("get_rho on a k-sharded object")
         self._kmesh()
         dms, ddms = _dms_to_dev(self, dm)
-        f = self._grid_aos()
-        nk, ngrid, nao = f.shape
         nset = ddms.shape[0]
-        rho = d.empty((nset, ngrid))
-        d.ctx.call("fisdf_get_rho", _lib.ptr(f), ngrid * nao, nk, ngrid, nao, _lib.ptr(ddms), nset,
-                   _lib.ptr(rho))
-        out = d.to_host(rho)
+        if xctype == "GGA":
+            out = _get_rho_gga(self, ddms, nset, hermi)
+            check = out[:, 0]
+        else:
+            f = self._grid_aos()
+            nk, ngrid, nao = f.shape
+            rho = d.empty((nset, ngrid))
+            d.ctx.call("fisdf_get_rho", _lib.ptr(f), ngrid * nao, nk, ngrid, nao, _lib.ptr(ddms),
+                       nset, _lib.ptr(rho))
+            out = check = d.to_host(rho)
         if hermi == 1:
-            if abs(out.imag).max() > 1e-10 * abs(out).max():
+            if abs(check.imag).max() > 1e-10 * abs(check).max():
                 raise ValueError("get_rho(hermi=1): the density is not real (max |Im rho| = "
-                                 f"{abs(out.imag).max():.3e}); pass hermi=0 for general dms")
+                                 f"{abs(check.imag).max():.3e}); pass hermi=0 for general dms")
             out = np.ascontiguousarray(out.real)
         nd = np.ndim(dm)
         return out[0] if nd < 4 else out
+
+    def deriv_block_points(self, kpts=None):
+        """Grid points per block of the AO values with first derivatives that ``deriv_work_bytes``
+        allows, for the k-mesh (None) or for ``kpts``."""
+        self._kmesh()
+        return _deriv_plan(self, kpts)[0]
+
+    def nr_vxc_mat(self, wv, kpts=None, xctype=None):
+        """The exchange-correlation potential matrices of a caller's functional derivatives on
+        the FFT grid (PySCF ``KNumInt.nr_rks``' matrix step; the functional itself stays with the
+        caller).  GGA: ``wv`` (4, ngrid) or (nset, 4, ngrid) real, wv[0] = de/drho and
+        wv[1:4] = 2 de/dsigma grad rho, unweighted (the quadrature weight vol/ngrid is applied
+        here):
+          V_k[m,n] = (vol/ngrid) sum_g { wv_0 conj f[g,m] f[g,n]
+                     + sum_c wv_c (conj d_c f[g,m] f[g,n] + conj f[g,m] d_c f[g,n]) }
+        (``aow = 1/2 wv_0 f + sum_c wv_c d_c f; V = f^H aow + h.c.``), Hermitian by construction.
+        LDA: ``wv`` (ngrid,) or (nset, ngrid), V = (vol/ngrid) f^H wv f over the resident AOs.
+        A 2-D ``wv`` of shape (4, ngrid) is read as one GGA set unless xctype="LDA" says
+        otherwise.  Returns (..., nk, nao, nao) on the host: at the k-mesh (kpts None), at (n, 3)
+        ``kpts`` ((n, nao, nao)) or at one (3,) k-point ((nao, nao)); points off the mesh go
+        through the band evaluator.  No build() needed."""
+        return _nr_vxc_mat(self, wv, kpts, xctype)
+
+    def get_kin(self, kpts=None):
+        """The kinetic matrices by the FFT-grid quadrature,
+          T_k[m,n] = 1/2 (vol/ngrid) sum_g sum_c conj d_c f_k[g,m] d_c f_k[g,n],
+        the companion of ``get_ovlp``: the quadrature ``get_ovlp``, ``get_pp`` and the exact J
+        use, so that ``get_pp() + get_kin()`` is a core Hamiltonian on one grid.  It is NOT
+        PySCF's analytic ``pbc_intor('int1e_kin')``: it converges to it with the mesh, and a
+        steep basis function needs a fine mesh.  Arguments and shapes as ``get_pp``; at Gamma
+        the imaginary part is set to zero.  No build() needed."""
+        return _get_kin(self, kpts)
 
     def get_pp(self, kpts=None):
         """``FFTDF.get_pp(kpts)`` [pyscf]: the GTH pseudopotential matrices V^loc + V^nl of
@@ -1202,6 +1255,191 @@ def _band_grid_aos(df_obj, coords, kb):
         from .ao import eval_ao_band_gpu
         return eval_ao_band_gpu(df_obj.device, cell, coords, kb)
     return df_obj.device.to_dev(bloch_ao(cell, coords, kb))   # a PySCF-protocol cell
+
+
+def _mesh_index(df_obj, kp):
+    """Indices of kp on the k-mesh, or None when a point is off the mesh (or a mesh point
+    shifted by a reciprocal vector)."""
+    try:
+        idx, _ = df_obj._kidx(kp)
+    except ValueError:
+        return None
+    if abs(np.asarray(df_obj.kpts)[idx] - kp).max() > 1e-9:
+        return None
+    return idx
+
+
+def _deriv_plan(df_obj, kpts):
+    """(nb, kp, idx, tn) of a walk over the FFT grid in blocks of the AO values with first
+    derivatives: nb points per block from ``deriv_work_bytes``, kp the k-points (None: the
+    k-mesh), idx their k-mesh indices (None: off the mesh, band evaluator), tn the lattice
+    translations of the whole grid (None for a cell evaluated on the host)."""
+    cell = df_obj.cell
+    nao = cell.nao_nr()
+    kp = None if kpts is None else np.asarray(kpts, float).reshape(-1, 3)
+    idx = None if kp is None else _mesh_index(df_obj, kp)
+    mesh = kp is None or idx is not None
+    nk = len(df_obj.kpts) if mesh else len(kp)
+    tn = None
+    per_point, fixed = 64 * nk * nao, 0
+    if df_obj.ao_on_gpu and hasattr(cell, "shells"):
+        from .cell import lattice_translations
+        tn = lattice_translations(cell, df_obj.grids_coords())
+        nimg = nk if mesh else max(len(tn), 1)
+        per_point += 32 * nimg * nao                      # the folded images, four components
+        fixed = (1 << 20) + 4096 + 24 * len(tn) + (0 if mesh else (16 * nk + 4) * len(tn))
+    nb = (int(df_obj.deriv_work_bytes) - fixed) // per_point
+    if nb < 1:
+        raise ValueError(f"deriv_work_bytes = {df_obj.deriv_work_bytes} is below one grid point "
+                         f"of the AO derivative block ({per_point} bytes a point + {fixed})")
+    return int(nb), kp, idx, tn
+
+
+def _deriv_blocks(df_obj, plan):
+    """Yield (g0, g1, f4) over the FFT grid: f4 the device block (nk, 4, g1 - g0, nao)."""
+    nb, kp, idx, tn = plan
+    cell, d = df_obj.cell, df_obj.device
+    coords = df_obj.grids_coords()
+    kmesh = df_obj._kmesh()
+    mesh = kp is None or idx is not None
+    on_gpu = df_obj.ao_on_gpu and hasattr(cell, "shells")
+    sub = None
+    if idx is not None and not (len(idx) == len(df_obj.kpts)
+                                and np.array_equal(idx, np.arange(len(idx)))):
+        sub = idx.astype(np.int64)
+    for g0 in range(0, len(coords), nb):
+        g1 = min(g0 + nb, len(coords))
+        if on_gpu:
+            from .ao import eval_ao_band_gpu, eval_ao_kpts_gpu
+            if mesh:
+                f4 = eval_ao_kpts_gpu(d, cell, coords[g0:g1], kmesh, deriv=1, tn=tn)
+            else:
+                f4 = eval_ao_band_gpu(d, cell, coords[g0:g1], kp, deriv=1, tn=tn)
+        else:       # a PySCF-protocol cell: pbc_eval_gto("GTOval_sph_deriv1"), uploaded
+            blk = max(1, int(df_obj.blksize))
+            f4 = d.empty((len(df_obj.kpts) if mesh else len(kp), 4, g1 - g0, cell.nao_nr()))
+            for h0 in range(g0, g1, blk):
+                h1 = min(h0 + blk, g1)
+                f4[:, :, h0 - g0:h1 - g0] = d.to_dev(
+                    bloch_ao(cell, coords[h0:h1], df_obj.kpts if mesh else kp,
+                             kmesh if mesh else None, deriv=1))
+        if sub is not None:
+            f4 = f4[d.torch.as_tensor(sub, device=f4.device)].contiguous()
+        yield g0, g1, f4
+        del f4
+
+
+def _get_rho_gga(df_obj, ddms, nset, hermi):
+    """rho and its gradient (nset, 4, ngrid) complex on the host (fisdf_get_rho_gga per block)."""
+    if hermi not in (0, 1):
+        raise ValueError(f"get_rho: hermi must be 0 or 1, not {hermi!r}")
+    d = df_obj.device
+    ngrid = int(np.prod(df_obj.mesh))
+    rho = d.empty((nset, 4, ngrid))
+    flat = rho.view(-1)
+    for g0, g1, f4 in _deriv_blocks(df_obj, _deriv_plan(df_obj, None)):
+        nk, _, nb, nao = f4.shape
+        d.ctx.call("fisdf_get_rho_gga", _lib.ptr(f4), 4 * nb * nao, nb * nao, nk, nb, nao,
+                   _lib.ptr(ddms), nset, int(hermi), _lib.ptr(flat[g0:]), ngrid)
+    return d.to_host(rho)
+
+
+def _nr_vxc_mat(df_obj, wv, kpts, xctype):
+    d = df_obj.device
+    if d.sharded(df_obj):
+        raise NotImplementedError("nr_vxc_mat on a k-sharded object")
+    df_obj._kmesh()
+    cell = df_obj.cell
+    ngrid = int(np.prod(df_obj.mesh))
+    nao = cell.nao_nr()
+    w = np.asarray(wv)
+    if xctype is not None and xctype not in df_obj.XCTYPES:
+        raise ValueError(f"nr_vxc_mat: xctype must be one of {list(df_obj.XCTYPES)} or None, "
+                         f"not {xctype!r}")
+    if np.iscomplexobj(w):
+        raise ValueError("nr_vxc_mat: wv must be real")
+    if xctype is None:
+        xctype = "GGA" if w.ndim == 3 or (w.ndim == 2 and w.shape[0] == 4) else "LDA"
+    gga = xctype == "GGA"
+    want = ((4, ngrid), (None, 4, ngrid)) if gga else ((ngrid,), (None, ngrid))
+    if not any(w.ndim == len(t) and all(a is None or a == b for a, b in zip(t, w.shape))
+               for t in want) or w.size == 0:
+        raise ValueError(f"nr_vxc_mat: wv of shape {w.shape} is neither {want[0]} nor "
+                         f"(nset,) + {want[0]} for xctype {xctype}")
+    has_set = w.ndim == len(want[1])
+    w = np.ascontiguousarray(w.reshape((-1,) + want[0]), dtype=np.float64)
+    nset = w.shape[0]
+    single = kpts is not None and np.ndim(kpts) == 1
+    scale = cell.vol / ngrid
+    if gga:
+        plan = _deriv_plan(df_obj, kpts)
+        dw = d.torch.as_tensor(w, device=d.dev).view(-1)
+        out = None
+        for g0, g1, f4 in _deriv_blocks(df_obj, plan):
+            nk, _, nb, _ = f4.shape
+            if out is None:
+                out = d.empty((nset, nk, nao, nao))
+            d.ctx.call("fisdf_gga_gram", _lib.ptr(f4), 4 * nb * nao, nb * nao, nk, nb, nao,
+                       _lib.ptr(dw[g0:]), 4 * ngrid, ngrid, nset, scale, 1 if g0 else 0,
+                       _lib.ptr(out))
+        v = d.to_host(out)
+    else:
+        kp = df_obj.kpts if kpts is None else np.asarray(kpts, float).reshape(-1, 3)
+        idx = np.arange(len(kp)) if kpts is None else _mesh_index(df_obj, kp)
+        dv = d.to_dev(w.astype(np.complex128))
+
+        def run(f):
+            o = d.empty((nset, f.shape[0], nao, nao))
+            d.ctx.call("fisdf_weighted_gram", _lib.ptr(f), ngrid * nao, f.shape[0], ngrid, nao,
+                       _lib.ptr(dv), nset, 0, scale, _lib.ptr(o))
+            return d.to_host(o)
+
+        if idx is not None:
+            f = df_obj._grid_aos()
+            if not (len(idx) == f.shape[0] and np.array_equal(idx, np.arange(f.shape[0]))):
+                f = f[d.torch.as_tensor(idx.astype(np.int64), device=f.device)].contiguous()
+            v = run(f)
+        else:
+            blk = max(1, int(BAND_BLOCK_BYTES // (16 * ngrid * nao)))
+            coords = df_obj.grids_coords()
+            v = np.empty((nset, len(kp), nao, nao), complex)
+            for b0 in range(0, len(kp), blk):
+                fb = _band_grid_aos(df_obj, coords, kp[b0:b0 + blk])
+                v[:, b0:b0 + blk] = run(fb)
+                del fb
+    if single:
+        v = v[:, 0]
+    return v if has_set else v[0]
+
+
+def _get_kin(df_obj, kpts):
+    d = df_obj.device
+    if d.sharded(df_obj):
+        raise NotImplementedError("get_kin on a k-sharded object")
+    df_obj._kmesh()
+    cell = df_obj.cell
+    ngrid = int(np.prod(df_obj.mesh))
+    nao = cell.nao_nr()
+    single = kpts is not None and np.ndim(kpts) == 1
+    plan = _deriv_plan(df_obj, kpts)
+    kp = df_obj.kpts if plan[1] is None else plan[1]
+    alpha = np.array([0.5 * cell.vol / ngrid, 0.0])
+    beta = np.array([1.0, 0.0])
+    T = None
+    for g0, g1, f4 in _deriv_blocks(df_obj, plan):
+        nk, _, nb, _ = f4.shape
+        if T is None:
+            T = d.torch.zeros((nk, nao, nao), dtype=d.torch.complex128, device=f4.device)
+        flat = f4.view(-1)
+        for c in (1, 2, 3):     # T_k += 1/2 (vol/ngrid) (d_c f_k)^H (d_c f_k), in block order
+            fc = _lib.ptr(flat[c * nb * nao:])
+            d.ctx.call("fisdf_zgemm", 3, 0, nao, nao, nb, alpha.ctypes.data_as(_lib._dp), fc, nao,
+                       4 * nb * nao, fc, nao, 4 * nb * nao, beta.ctypes.data_as(_lib._dp),
+                       _lib.ptr(T), nao, nao * nao, nk, max(1, min(64, nb // 1024)))
+    t = d.to_host(T)
+    gamma = np.abs(kp).max(axis=1) < 1e-12
+    t[gamma] = t[gamma].real
+    return t[0] if single else t
 
 
 def _get_pp(df_obj, kpts, nuc):

@@ -273,6 +273,29 @@ int fisdf_eval_ao_band(fisdf_ctx* ctx, const void* d_coords, int ng, int natm, c
                        int nkb, const double* h_kpts, const double a[9], double rcut, int nao,
                        void* d_out);
 
+/* The values with their first derivatives: the arguments and the host checks of fisdf_eval_ao /
+ * fisdf_eval_ao_band, d_out (nk, 4, ng, nao) c128 — per k-point component 0 the value, 1..3
+ * d/dx, d/dy, d/dz (PySCF's eval_ao_kpts(..., deriv=1) layout):
+ *   d_c chi_k(r) = sum_T e^{ik.T} d_c phi(r - T),   same mask |r - A - T|^2 < rcut^2,
+ *   d_c [R(r^2) S_lm(d)] = R' 2 d_c S_lm + R d_c S_lm,   R' = -sum_p alpha_p c_p e^{-alpha_p r^2},
+ * the gradients of the solid harmonics as polynomials (no division by r: a point on an atom gives
+ * the finite p gradient and zeros for d and f).  One exponential per primitive serves the four
+ * components, the translations of an image are summed in list order, and component 0 equals
+ * fisdf_eval_ao's output bit for bit.  The four real components pass the k-mesh transform / band
+ * tail of the value entries as 4 ng nao columns.  Workspace: the context's arena, four times the
+ * value entries' folded images. */
+int fisdf_eval_ao_deriv1(fisdf_ctx* ctx, const void* d_coords, int ng, int natm,
+                         const double* h_atoms, int nsh, const int* h_sh_atom, const int* h_sh_l,
+                         const int* h_sh_nprim, const double* h_exps, const double* h_coefs, int nT,
+                         const int* h_tn, const int kmesh[3], const double a[9], double rcut,
+                         int nao, void* d_out);
+int fisdf_eval_ao_band_deriv1(fisdf_ctx* ctx, const void* d_coords, int ng, int natm,
+                              const double* h_atoms, int nsh, const int* h_sh_atom,
+                              const int* h_sh_l, const int* h_sh_nprim, const double* h_exps,
+                              const double* h_coefs, int nT, const int* h_tn, int nkb,
+                              const double* h_kpts, const double a[9], double rcut, int nao,
+                              void* d_out);
+
 /* ---- A1: interpolation-point selection ------------------------------------
  * Replaces InterpolativeSeparableDensityFitting.select_interpolation_points
  * (fftisdf.py:357-388): x2 = sum_q Re(x0_q^* x0_q^T); x4 = x2*x2/nk; greedy pivoted
@@ -530,6 +553,37 @@ int fisdf_coulomb_potential(fisdf_ctx* ctx, const void* d_rho, int nset, const i
  * and the partial blocks are summed in split order. */
 int fisdf_weighted_gram(fisdf_ctx* ctx, const void* d_f, long f_kstride, int nk, int ngrid,
                         int nao, const void* d_v, int nset, int conj_v, double scale, void* d_out);
+/* ---- GGA density and potential matrix over a block of AO values with first derivatives ------
+ * d_f4: component c (0 the value, 1..3 d/dx, d/dy, d/dz) of k-point k at d_f4 + k f_kstride +
+ * c f_cstride, (ng, nao) c128 each, both strides >= ng * nao (fisdf_eval_ao_deriv1's output:
+ * f_kstride = 4 ng nao, f_cstride = ng nao).  ng is a block of the grid: the four-component array
+ * of a whole FFT grid is not meant to be resident.
+ *
+ * d_rho[(s 4 + c) rho_cstride + g], complex, rho_cstride >= ng (a block writes into a whole-grid
+ * array (nset, 4, ngrid) through an offset pointer and rho_cstride = ngrid):
+ *   rho_0   = (1/nk) sum_k sum_mn f[g,m] D[s][k][m,n] conj f[g,n]          (fisdf_get_rho's sum)
+ *   d_c rho = (1/nk) sum_k sum_mn (d_c f[g,m] D[m,n] conj f[g,n] + f[g,m] D[m,n] conj d_c f[g,n])
+ * hermi = 1 (D Hermitian): d_c rho = (2/nk) sum_k Re sum_n t[g,n] conj d_c f[g,n], t = f D the
+ * row rho_0 forms anyway — three real dot products more per point, imaginary part exactly 0.
+ * hermi = 0: both terms (a second row u[n] = sum_m f[g,m] conj D[n,m] stands for the first).
+ * One pass over d_f4 serves up to 4 sets (2 for hermi = 0 with nao > 32).  No atomics, a fixed
+ * summation order: repeated calls agree bit for bit, and a point's result does not depend on the
+ * block it is in.  Refused on the host with d_rho untouched: a size < 1, a stride below its
+ * minimum, hermi other than 0 or 1.  Asynchronous. */
+int fisdf_get_rho_gga(fisdf_ctx* ctx, const void* d_f4, long f_kstride, long f_cstride, int nk,
+                      int ng, int nao, const void* d_dms, int nset, int hermi, void* d_rho,
+                      long rho_cstride);
+/* d_out[s][k][m,n] (+)= scale sum_g { w_0 conj f[g,m] f[g,n]
+ *                        + sum_c w_c (conj d_c f[g,m] f[g,n] + conj f[g,m] d_c f[g,n]) },
+ * w real doubles, d_w[s w_sstride + c w_cstride + g] (both strides >= ng), d_out (nset, nk, nao,
+ * nao); accumulate = 0 overwrites, else adds to what d_out holds.  PySCF's aow = 1/2 w_0 f +
+ * sum_c w_c d_c f; M = f^H aow; V = M + M^H: aow by an elementwise kernel into the arena, M by
+ * the batched split-K GEMM, then M + M^H.  Hermitian bit for bit (the diagonal exactly real) when
+ * what it accumulates onto is, no atomics, repeated calls agree bit for bit.  The LDA case
+ * (w (nset, ng)) is fisdf_weighted_gram.  Workspace: the context's arena.  Asynchronous. */
+int fisdf_gga_gram(fisdf_ctx* ctx, const void* d_f4, long f_kstride, long f_cstride, int nk, int ng,
+                   int nao, const void* d_w, long w_sstride, long w_cstride, int nset, double scale,
+                   int accumulate, void* d_out);
 /* The three stages back to back with scale = vol / ngrid: d_vj (nset, nk, nao, nao) for the
  * k-mesh, or, with d_fband (nband, ngrid, nao) the AOs at band k-points on the same grid,
  * d_vj (nset, nband, nao, nao) at those (d_fband NULL: the k-mesh).  rho and v live in the
