@@ -4,6 +4,7 @@
 #include "../../include/fisdf.h"
 
 #include <algorithm>
+#include <climits>
 #include <cstdlib>
 #include <cmath>
 #include <cstring>
@@ -1815,9 +1816,12 @@ int fisdf_unpack_slices(fisdf_ctx* c, const void* recv, int nrows, int nparts, c
                         const long* h_ng, long ngrid, void* yT) {
   FISDF_TRY(device_guard(c));
   StageTimer tm(c, FISDF_ST_Y);
+  FISDF_CHECK(nrows >= 0 && nparts >= 0 && (nparts == 0 || (h_g0 && h_ng)), "unpack: bad sizes");
+  for (int p = 0; p < nparts; ++p)  // every slice before the first copy: a refused call writes nothing
+    FISDF_CHECK(h_g0[p] >= 0 && h_ng[p] >= 0 && h_g0[p] + h_ng[p] <= ngrid, "unpack: bad slice");
+  FISDF_CHECK(nrows == 0 || nparts == 0 || (recv && yT), "unpack: null buffer");
   const char* src = (const char*)recv;
   for (int p = 0; p < nparts; ++p) {
-    FISDF_CHECK(h_g0[p] >= 0 && h_ng[p] >= 0 && h_g0[p] + h_ng[p] <= ngrid, "unpack: bad slice");
     if (h_ng[p] == 0 || nrows == 0) continue;
     FISDF_HIP(hipMemcpy2DAsync((char*)yT + sizeof(cplx) * h_g0[p], sizeof(cplx) * ngrid, src,
                                sizeof(cplx) * h_ng[p], sizeof(cplx) * h_ng[p], nrows,
@@ -3473,10 +3477,18 @@ int fisdf_build_ws(fisdf_ctx* c, const void* Wqv, int q0, int q1, int nip, const
 int fisdf_get_eri(fisdf_ctx* c, const void* Xv, int nip, int nao, const int kidx[4],
                   const void* Wqv, const void* const* Cv, const int nmo[4], void* outv) {
   FISDF_TRY(device_guard(c));
+  FISDF_CHECK(Xv && Wqv && outv && kidx, "get_eri: null X, W, index list or output");
+  FISDF_CHECK(nip >= 1 && nao >= 1, "get_eri: nip and nao must be at least 1");
   const cplx* X = (const cplx*)Xv;
   int n[4];
-  for (int s = 0; s < 4; ++s) n[s] = Cv && Cv[s] ? nmo[s] : nao;
+  for (int s = 0; s < 4; ++s) {
+    FISDF_CHECK(kidx[s] >= 0, "get_eri: negative k index");
+    FISDF_CHECK(!(Cv && Cv[s]) || (nmo && nmo[s] >= 1), "get_eri: C_s given with nmo[s] < 1");
+    n[s] = Cv && Cv[s] ? nmo[s] : nao;
+  }
+  // the pair counts are GEMM dimensions (int), checked before the arena is asked for anything
   const long p12 = (long)n[0] * n[1], p34 = (long)n[2] * n[3];
+  FISDF_CHECK(p12 <= INT_MAX && p34 <= INT_MAX, "get_eri: n1*n2 or n3*n4 beyond int range");
   Carver cv;
   size_t oA[4];
   for (int s = 0; s < 4; ++s) oA[s] = cv.take(sizeof(cplx) * (size_t)nip * n[s]);
@@ -3514,6 +3526,8 @@ int fisdf_get_eri(fisdf_ctx* c, const void* Xv, int nip, int nao, const int kidx
 int fisdf_get_j_rows(fisdf_ctx* c, const void* Xv, const void* W0, const void* dmsv, int nset,
                      int nk, int nip, int nao, int i0, int i1, void* vjv) {
   FISDF_TRY(device_guard(c));
+  FISDF_CHECK(Xv && W0 && dmsv && vjv, "get_j: null X, W0, density matrices or output");
+  FISDF_CHECK(nset >= 1 && nk >= 1 && nip >= 1 && nao >= 1, "get_j: a size below 1");
   FISDF_CHECK(0 <= i0 && i0 <= i1 && i1 <= nip, "get_j: bad row range");
   StageTimer tm(c, FISDF_ST_J);
   const cplx* X = (const cplx*)Xv;
@@ -3556,6 +3570,9 @@ int fisdf_get_j_band_rows(fisdf_ctx* c, const void* Xv, const void* W0, const vo
                           int nk, int nip, int nao, const void* Xbv, int nkb, int i0, int i1,
                           void* vjv) {
   FISDF_TRY(device_guard(c));
+  FISDF_CHECK(Xv && W0 && dmsv && Xbv && vjv,
+              "get_j_band: null X, W0, density matrices, band AOs or output");
+  FISDF_CHECK(nset >= 1 && nk >= 1 && nip >= 1 && nao >= 1, "get_j_band: a size below 1");
   FISDF_CHECK(0 <= i0 && i0 <= i1 && i1 <= nip && nkb > 0, "get_j_band: bad sizes");
   StageTimer tm(c, FISDF_ST_J);
   const cplx* X = (const cplx*)Xv;
@@ -4318,11 +4335,23 @@ static int get_k_block(fisdf_ctx* c, const void* Xv, const double* Ws_rows, long
                        const void* dmsv, int nset, int nip, int nao, const int kmesh[3],
                        const double a[9], int i0, int i1, void* vkv);
 
+// the host checks of both row forms, made before anything is enqueued
+static int get_k_check(const void* Xv, const void* Wsv, const void* dmsv, int nset, int nip,
+                       int nao, const int kmesh[3], const double a[9], int i0, int i1,
+                       const void* vkv) {
+  FISDF_CHECK(Xv && Wsv && dmsv && vkv && kmesh && a,
+              "get_k: null X, W_s, density matrices, k-mesh, lattice or output");
+  FISDF_CHECK(nset >= 1 && nip >= 1 && nao >= 1, "get_k: a size below 1");
+  FISDF_TRY(kmesh_check(kmesh, "get_k"));
+  FISDF_CHECK(0 <= i0 && i0 <= i1 && i1 <= nip, "get_k: bad row range");
+  return 0;
+}
+
 int fisdf_get_k_rows(fisdf_ctx* c, const void* Xv, const void* Wsv, const void* dmsv, int nset,
                      int nip, int nao, const int kmesh[3], const double a[9], int i0, int i1,
                      void* vkv) {
   FISDF_TRY(device_guard(c));
-  FISDF_CHECK(0 <= i0 && i0 <= i1 && i1 <= nip, "get_k: bad row range");
+  FISDF_TRY(get_k_check(Xv, Wsv, dmsv, nset, nip, nao, kmesh, a, i0, i1, vkv));
   // rows i0.. of W_s[R] inside the full (nk, nip, nip) array
   return get_k_block(c, Xv, (const double*)Wsv + (long)i0 * nip, (long)nip * nip, dmsv, nset, nip,
                      nao, kmesh, a, i0, i1, vkv);
@@ -4332,7 +4361,7 @@ int fisdf_get_k_rows_local(fisdf_ctx* c, const void* Xv, const void* Ws_rows, co
                            int nset, int nip, int nao, const int kmesh[3], const double a[9],
                            int i0, int i1, void* vkv) {
   FISDF_TRY(device_guard(c));
-  FISDF_CHECK(0 <= i0 && i0 <= i1 && i1 <= nip, "get_k: bad row range");
+  FISDF_TRY(get_k_check(Xv, Ws_rows, dmsv, nset, nip, nao, kmesh, a, i0, i1, vkv));
   // this rank's rows only: (nk, i1 - i0, nip) from fisdf_build_ws_rows + a reduce-scatter
   return get_k_block(c, Xv, (const double*)Ws_rows, (long)(i1 - i0) * nip, dmsv, nset, nip, nao,
                      kmesh, a, i0, i1, vkv);

@@ -65,7 +65,11 @@ int fisdf_memcpy_dtoh(fisdf_ctx* ctx, void* h_dst, const void* d_src, size_t byt
 int fisdf_set_timing(fisdf_ctx* ctx, int enable);
 int fisdf_timings(fisdf_ctx* ctx, double* h_ms /* FISDF_NSTAGES */, int* h_calls); /* synchronous; resets */
 /* reality invariants, max |Im| seen since the last call: [0] x2_s (fftisdf.py:43),
- * [1] fx_s (fftisdf.py:81), [2] rho_s (fftisdf.py:216).  synchronous; resets. */
+ * [1] fx_s (fftisdf.py:81), [2] rho_s (fftisdf.py:216).  synchronous; resets.
+ * [2] covers what fisdf_get_k(_rows, _rows_local) transformed since the last call: for a row
+ * block [i0, i1) the entries rho_s[R, J, I] with I in the block and every J, R and set (the ones
+ * that enter the block's V_s), nothing for an empty block; an absolute value, to be judged against
+ * max |rho_s|. */
 int fisdf_max_imag(fisdf_ctx* ctx, double* h_out /* 3 */);
 
 /* ---- composite entries: the whole 1-GPU build and get_jk ----------------
@@ -324,6 +328,8 @@ int fisdf_select_pivots(fisdf_ctx* ctx, const void* d_x2, int nk, int ng0, int n
 
 /* Reassemble a k-shard's y after the grid-slice all-to-all: d_recv holds, for p = 0..nparts-1,
  * a (nrows, h_ng[p]) block of grid points [h_g0[p], h_g0[p]+h_ng[p]); d_yT is (nrows, ngrid). */
+/* Every slice is checked before the first copy: a slice outside [0, ngrid) (or a negative count)
+ * is refused with d_yT untouched.  Slices may come in any order and may be empty. */
 int fisdf_unpack_slices(fisdf_ctx* ctx, const void* d_recv, int nrows, int nparts,
                         const long* h_g0, const long* h_ng, long ngrid, void* d_yT);
 
@@ -502,14 +508,23 @@ int fisdf_build_ws_blocks(fisdf_ctx* ctx, const void* d_Wq, const int* h_qs, con
 int fisdf_get_j(fisdf_ctx* ctx, const void* d_X, const void* d_W0, const void* d_dms, int nset,
                 int nk, int nip, int nao, void* d_vj);
 
-/* ---- A8: get_k_kpts (fftisdf.py:173-228) ------------------------------------ */
+/* ---- A8: get_k_kpts (fftisdf.py:173-228) ------------------------------------
+ * rho_k = X_k D_k X_k^H / nk; rho_s = Phi rho_k; V_s[R,I,J] = W_s[R,I,J] Re(rho_s[R,J,I]);
+ * V_k = Phi^T V_s; K_k = X_k^H V_k X_k.  Only Re(rho_s) enters V_s (the reference asserts
+ * |Im rho_s| < 1e-10 and drops it, :216-217): for density matrices without D_{-k} = conj(D_k), or
+ * AOs without X_{-k} = conj(X_k), Im(rho_s) is not small, it is still dropped, and slot 2 of
+ * fisdf_max_imag reports its size. */
 int fisdf_get_k(fisdf_ctx* ctx, const void* d_X, const void* d_Ws, const void* d_dms, int nset,
                 int nip, int nao, const int kmesh[3], const double a[9], void* d_vk);
 
 /* Row-block forms: the contribution of the interpolation points I in [i0, i1) to J / K
  * (J_k = sum_I X_k[I]^H v_I X_k[I], K_k = sum_I X_k[I]^H (V_k[I,:] X_k)); the full result is
  * the sum over a partition of [0, nip) — a sharded caller all-reduces nset*nk*nao^2 values.
- * fisdf_get_j / fisdf_get_k are the [0, nip) cases. */
+ * fisdf_get_j / fisdf_get_k are the [0, nip) cases (the same launches, bit for bit); an empty
+ * block writes zeros.  Refused on the host, before anything is enqueued and with the output
+ * untouched: a null X, W, density-matrix or output pointer (K: a null k-mesh or lattice), nset, nk,
+ * nip or nao below 1, a row range outside 0 <= i0 <= i1 <= nip, a k-mesh axis outside 1..16, and
+ * for the band form nkb < 1 or a null d_Xb. */
 int fisdf_get_j_rows(fisdf_ctx* ctx, const void* d_X, const void* d_W0, const void* d_dms,
                      int nset, int nk, int nip, int nao, int i0, int i1, void* d_vj);
 int fisdf_get_k_rows(fisdf_ctx* ctx, const void* d_X, const void* d_Ws, const void* d_dms,
@@ -810,7 +825,14 @@ int fisdf_pp_plan(int nao, long ngrid, int nk, int np, const fisdf_pp_atom* h_at
  * eri[i*n2+j][k*n4+l] = sum_IJ W_q[I,J] conj(A1[I,i]) A2[I,j] conj(A3[J,k]) A4[J,l] with
  * A_s = X_{kidx[s]} C_s, q = k2 - k1 (fftdf-with-k-lstsq.py:221-232).  d_Wq: the (nip,nip)
  * W of that q; h_dC: host array of 4 DEVICE pointers to (nao, nmo[s]) MO coefficients, or
- * NULL (or NULL entries) for AO integrals.  d_out: (n1*n2, n3*n4) c128. */
+ * NULL (or NULL entries) for AO integrals (nmo[s] is then not read).  d_out: (n1*n2, n3*n4) c128.
+ * W_q is taken as given: any complex matrix, nothing Hermitian assumed.
+ * kidx[s] selects X_{kidx[s]} inside d_X (nk, nip, nao).  The entry is not told nk, so it cannot
+ * check the upper end: 0 <= kidx[s] < nk is the caller's responsibility (the mirror maps k-points
+ * to indices and checks momentum conservation, isdf.py _kidx / _eri_isdf); a negative index is
+ * refused.  Also refused on the host, before the workspace is asked for and with d_out untouched:
+ * a null d_X, d_Wq, kidx or d_out, nip or nao below 1, a C_s given with nmo NULL or nmo[s] < 1,
+ * n1*n2 or n3*n4 beyond INT_MAX (they are GEMM dimensions). */
 int fisdf_get_eri(fisdf_ctx* ctx, const void* d_X, int nip, int nao, const int kidx[4],
                   const void* d_Wq, const void* const* h_dC, const int nmo[4], void* d_out);
 
