@@ -3694,6 +3694,96 @@ int fisdf_gga_gram(fisdf_ctx* c, const void* f4v, long f_kstride, long f_cstride
                   (cplx*)(b + oA), (cplx*)(b + oM), ns ? (cplx*)(b + oS) : nullptr);
 }
 
+int fisdf_xc_eval(fisdf_ctx* c, int family, double cx, double cc, double rho_cut, const void* rhov,
+                  long rho_sstride, long rho_cstride, int ng, int nset, void* ev, long e_sstride,
+                  void* wv, long w_sstride, long w_cstride) {
+  FISDF_TRY(device_guard(c));
+  StageTimer tm(c, FISDF_ST_J);
+  return xc_eval(c->stream, family, cx, cc, rho_cut, (const cplx*)rhov, rho_sstride, rho_cstride,
+                 ng, nset, (double*)ev, e_sstride, (double*)wv, w_sstride, w_cstride, nullptr);
+}
+
+}  // extern "C"
+
+namespace {
+
+// the arena of one fused block, carved in this order; bytes() <= per_point ng + fixed of
+// fisdf_nr_rks_plan (each of the seven pieces is rounded up to 256 bytes)
+struct NrRksArena {
+  size_t oRho, oW, oE, oPart, oAow, oM, oSplit, bytes;
+  size_t nsplit;
+};
+
+constexpr int kNrRksPieces = 7;
+
+void nr_rks_arena(int nk, int ng, int nao, int nset, NrRksArena* a) {
+  size_t na, nm, ns;
+  gga_gram_work(nk, ng, nao, &na, &nm, &ns);
+  Carver cv;
+  a->oRho = cv.take(sizeof(cplx) * (size_t)nset * 4 * ng);
+  a->oW = cv.take(sizeof(double) * (size_t)nset * 4 * ng);
+  a->oE = cv.take(sizeof(double) * (size_t)nset * ng);
+  a->oPart = cv.take(sizeof(double) * 2 * (size_t)nset * xc_blocks(ng));
+  a->oAow = cv.take(sizeof(cplx) * na);
+  a->oM = cv.take(sizeof(cplx) * nm);
+  a->oSplit = cv.take(sizeof(cplx) * ns);
+  a->nsplit = ns;
+  a->bytes = cv.off;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fisdf_nr_rks_plan(int nk, int ng, int nao, int nset, long* h_point_bytes, long* h_fixed_bytes) {
+  t_cur_ctx = nullptr;
+  FISDF_CHECK(nk >= 1 && ng >= 1 && nao >= 1 && nset >= 1, "nr_rks_plan: sizes must be >= 1");
+  FISDF_CHECK((long)nao * nao * nk < (1L << 31), "nr_rks_plan: matrices too large");
+  size_t na, nm, ns;
+  gga_gram_work(nk, ng, nao, &na, &nm, &ns);
+  // per point: rho 64 B, wv 32 B and e 8 B a set, and the gram's aow row of every k-point
+  if (h_point_bytes) *h_point_bytes = 104L * nset + 16L * nk * nao;
+  if (h_fixed_bytes)
+    *h_fixed_bytes = (long)(sizeof(cplx) * (nm + ns)) + 16L * nset * xc_blocks(ng) +
+                     256L * kNrRksPieces;
+  return 0;
+}
+
+int fisdf_nr_rks_block(fisdf_ctx* c, int family, double cx, double cc, double rho_cut,
+                       const void* f4v, long f_kstride, long f_cstride, int nk, int ng, int nao,
+                       const void* dmsv, int nset, double scale, int accumulate, void* vxcv,
+                       void* sumsv) {
+  FISDF_TRY(device_guard(c));
+  // every check of the three stages, before the first launch
+  FISDF_CHECK(family == 1, "nr_rks_block: family must be FISDF_XC_GGA (the LDA step takes the "
+                           "resident AOs: fisdf_get_rho, fisdf_xc_eval, fisdf_weighted_gram)");
+  FISDF_CHECK(f4v && dmsv && vxcv && sumsv, "nr_rks_block: null pointer");
+  FISDF_CHECK(nk >= 1 && ng >= 1 && nao >= 1 && nset >= 1, "nr_rks_block: sizes must be >= 1");
+  FISDF_CHECK(f_cstride >= (long)ng * nao, "nr_rks_block: f_cstride below ng * nao");
+  FISDF_CHECK(f_kstride >= (long)ng * nao, "nr_rks_block: f_kstride below ng * nao");
+  FISDF_CHECK((long)nao * nao * nk < (1L << 31), "nr_rks_block: density matrices too large");
+  FISDF_CHECK(((long)ng * nao * nk + 255) / 256 < (1L << 31), "nr_rks_block: block too large");
+  FISDF_CHECK((long)nset * 4 * ng < (1L << 40), "nr_rks_block: block too large");
+  FISDF_CHECK(std::isfinite(scale), "nr_rks_block: scale must be finite");
+  FISDF_TRY(xc_check(family, cx, cc, rho_cut, ng, nset, 4L * ng, ng, ng, 4L * ng, ng, true, true));
+  StageTimer tm(c, FISDF_ST_J);
+  NrRksArena a;
+  nr_rks_arena(nk, ng, nao, nset, &a);
+  void* base;
+  FISDF_TRY(arena_get(c, a.bytes, &base));
+  char* b = (char*)base;
+  cplx* rho = (cplx*)(b + a.oRho);
+  double *w = (double*)(b + a.oW), *e = (double*)(b + a.oE), *part = (double*)(b + a.oPart);
+  FISDF_TRY(rho_grid_gga(c->stream, (const cplx*)f4v, f_kstride, f_cstride, nk, ng, nao,
+                         (const cplx*)dmsv, nset, 1, rho, ng));
+  FISDF_TRY(xc_eval(c->stream, family, cx, cc, rho_cut, rho, 4L * ng, ng, ng, nset, e, ng, w,
+                    4L * ng, ng, part));
+  FISDF_TRY(gga_gram(c->stream, (const cplx*)f4v, f_kstride, f_cstride, nk, ng, nao, w, 4L * ng,
+                     ng, nset, scale, accumulate, (cplx*)vxcv, (cplx*)(b + a.oAow),
+                     (cplx*)(b + a.oM), a.nsplit ? (cplx*)(b + a.oSplit) : nullptr));
+  return xc_sums(c->stream, part, xc_blocks(ng), nset, scale, accumulate, (double*)sumsv);
+}
+
 int fisdf_coulomb_potential(fisdf_ctx* c, const void* rhov, int nset, const int mesh[3],
                             const double a[9], double omega, void* vv) {
   FISDF_TRY(device_guard(c));

@@ -220,6 +220,20 @@ int gga_gram(hipStream_t s, const cplx* f4, long fks, long fcs, int nk, int ng, 
              const double* w, long wss, long wcs, int nset, double scale, int accumulate, cplx* out,
              cplx* aow, cplx* M, cplx* split);
 
+// ---- the functional at the grid points of a block (func.hip) -----------------------------------
+// family 0 LDA (Slater + PW92), 1 GGA (PBE); rho[s rss + c rcs + g] complex, the real parts read;
+// e[s ess + g], wv[s wss + c wcs + g] real, either may be null.  part (optional): xc_blocks(ng)
+// pairs (sum n, sum e) per set, which xc_sums adds in a fixed order into sums[s][2].  xc_check
+// is xc_eval's argument check alone (for callers that must refuse before their first launch)
+int xc_blocks(int ng);
+int xc_check(int family, double cx, double cc, double rho_cut, int ng, int nset, long rss, long rcs,
+             long ess, long wss, long wcs, bool has_e, bool has_wv);
+int xc_eval(hipStream_t s, int family, double cx, double cc, double rho_cut, const cplx* rho,
+            long rss, long rcs, int ng, int nset, double* e, long ess, double* wv, long wss,
+            long wcs, double* part);
+int xc_sums(hipStream_t s, const double* part, int nblk, int nset, double scale, int accumulate,
+            double* sums);
+
 // ---- exact FFT-grid K (kfft.hip; PySCF fft_jk.get_k_kpts) in its two forms: the dm form, nao
 // transform rows per row m, and the occupied-orbital (low-rank) form below ----
 constexpr int kKfftGT = 64;        // grid points per tile of the kernels (one per lane)

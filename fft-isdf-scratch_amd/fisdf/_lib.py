@@ -97,6 +97,11 @@ _SIGS = {
     # GGA density and potential matrix over the four-component AO block
     "fisdf_get_rho_gga": ([_vp, _vp, _l, _l, _i, _i, _i, _vp, _i, _i, _vp, _l], _i),
     "fisdf_gga_gram": ([_vp, _vp, _l, _l, _i, _i, _i, _vp, _l, _l, _i, _d, _i, _vp], _i),
+    # the functional on a block, the fused RKS block and its arena
+    "fisdf_xc_eval": ([_vp, _i, _d, _d, _d, _vp, _l, _l, _i, _i, _vp, _l, _vp, _l, _l], _i),
+    "fisdf_nr_rks_block": ([_vp, _i, _d, _d, _d, _vp, _l, _l, _i, _i, _i, _vp, _i, _d, _i, _vp,
+                            _vp], _i),
+    "fisdf_nr_rks_plan": ([_i, _i, _i, _i, C.POINTER(_l), C.POINTER(_l)], _i),
     "fisdf_coulomb_potential": ([_vp, _vp, _i, _ip, _dp, _d, _vp], _i),
     "fisdf_weighted_gram": ([_vp, _vp, _l, _i, _i, _i, _vp, _i, _i, _d, _vp], _i),
     "fisdf_get_j_fft": ([_vp, _vp, _l, _ip, _ip, _dp, _i, _vp, _i, _d, _vp, _i, _vp], _i),

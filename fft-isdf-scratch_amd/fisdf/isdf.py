@@ -24,6 +24,7 @@ import time
 import numpy as np
 
 from . import _lib, kshard
+from . import xc as _xc
 from .cell import bloch_ao, madelung, make_kpts
 
 log = logging.getLogger("fisdf")
@@ -199,6 +200,8 @@ class InterpolativeSeparableDensityFitting:
     # at nk 64, 36^3, nao 26).  Below one point: ValueError
     deriv_work_bytes = 512 << 20
     XCTYPES = ("LDA", "GGA")
+    # eval_xc / nr_rks: a grid point with rho <= xc_rho_cut contributes nothing (e = 0, wv = 0)
+    xc_rho_cut = 1e-15
 
     def __init__(self, cell, kpts, m0=None, c0=20.0, device=None, comm=None):
         self.cell = cell
@@ -586,6 +589,46 @@ class InterpolativeSeparableDensityFitting:
         steep basis function needs a fine mesh.  Arguments and shapes as ``get_pp``; at Gamma
         the imaginary part is set to zero.  No build() needed."""
         return _get_kin(self, kpts)
+
+    def eval_xc(self, xc, rho):
+        """The functional ``xc`` (a name of ``fisdf.xc.FUNCTIONALS`` or a ``fisdf.xc.Functional``)
+        at the points of ``rho`` as ``get_rho`` returns it — GGA: (4, n) or (nset, 4, n), LDA:
+        (n,) or (nset, n), real (of a complex rho the real part is read); n is the grid or any
+        block of it.  Returns ``(e, wv)`` on the host: e (..., n) the energy per unit volume
+        (E_xc = vol/ngrid sum e), wv the unweighted ``wv`` of ``nr_vxc_mat`` ((..., 4, n) with
+        wv[0] = de/dn, wv[1:4] = 2 de/dsigma grad n; LDA (..., n)).  Points with n <=
+        ``xc_rho_cut`` give exact zeros.  fisdf_xc_eval; pointwise, so the result does not depend
+        on how the grid is cut into calls.  ``nr_vxc_mat(eval_xc(xc, get_rho(dm, xctype="GGA"))[1],
+        kpts=band)`` is V at band k-points."""
+        return _eval_xc(self, xc, rho)
+
+    def nr_rks_block_points(self, nset=1):
+        """Grid points per block of ``nr_rks`` for a GGA with ``nset`` density matrices:
+        ``deriv_work_bytes`` bounds the AO derivative block together with the arena of
+        fisdf_nr_rks_block (fisdf_nr_rks_plan), so it is at most ``deriv_block_points()``."""
+        self._kmesh()
+        return _nr_rks_plan(self, int(nset))[0]
+
+    def nr_rks(self, xc, dm, hermi=1):
+        """PySCF ``KNumInt.nr_rks``' ``(nelec, exc, vxc)`` of closed-shell density matrices
+        ``dm`` (nk, nao, nao) — floats and vxc (nk, nao, nao) — or (nset, nk, nao, nao), each set
+        an independent density — arrays (nset,) and vxc (nset, nk, nao, nao).  ``xc``: a name of
+        ``fisdf.xc.FUNCTIONALS`` ("lda", "pbe", "pbe0", "hf"), a ``fisdf.xc.Functional`` or a
+        callable.  For a hybrid this is the local part; the step is
+        ``vxc + vj - 0.5 * fisdf.hybrid_coeff(xc) * vk``.
+
+        GGA: one walk over the grid in blocks of the AO values with first derivatives, and per
+        block fisdf_nr_rks_block: the density with its gradient, the functional and the potential
+        matrix without leaving the device.  rho is ``get_rho(xctype="GGA")``'s, bit for bit;
+        nelec and exc add the block sums in block order: repeatable for a given
+        ``deriv_work_bytes``, equal up to rounding across budgets, as vxc is.  vxc is Hermitian
+        bit for bit.  LDA: the resident AOs, fisdf_get_rho, fisdf_xc_eval, fisdf_weighted_gram.
+        "hf": zeros, the device is not touched.  A callable ``f(rho) -> (e, wv)`` on host arrays
+        is treated as a GGA and called per block and set with rho (4, nb) real; it returns
+        e (nb,) per unit volume and wv (4, nb) as ``nr_vxc_mat`` takes it; the walk is the same,
+        with fisdf_get_rho_gga and fisdf_gga_gram around the call.  hermi must be 1.  No build()
+        needed."""
+        return _nr_rks(self, xc, dm, hermi)
 
     def get_pp(self, kpts=None):
         """``FFTDF.get_pp(kpts)`` [pyscf]: the GTH pseudopotential matrices V^loc + V^nl of
@@ -1269,11 +1312,12 @@ def _mesh_index(df_obj, kp):
     return idx
 
 
-def _deriv_plan(df_obj, kpts):
+def _deriv_plan(df_obj, kpts, arena=None):
     """(nb, kp, idx, tn) of a walk over the FFT grid in blocks of the AO values with first
     derivatives: nb points per block from ``deriv_work_bytes``, kp the k-points (None: the
     k-mesh), idx their k-mesh indices (None: off the mesh, band evaluator), tn the lattice
-    translations of the whole grid (None for a cell evaluated on the host)."""
+    translations of the whole grid (None for a cell evaluated on the host).  arena(nk, nao) ->
+    (bytes per point, fixed bytes) of a consumer's own workspace the budget has to hold too."""
     cell = df_obj.cell
     nao = cell.nao_nr()
     kp = None if kpts is None else np.asarray(kpts, float).reshape(-1, 3)
@@ -1288,6 +1332,9 @@ def _deriv_plan(df_obj, kpts):
         nimg = nk if mesh else max(len(tn), 1)
         per_point += 32 * nimg * nao                      # the folded images, four components
         fixed = (1 << 20) + 4096 + 24 * len(tn) + (0 if mesh else (16 * nk + 4) * len(tn))
+    if arena is not None:
+        ap, af = arena(nk, nao)
+        per_point, fixed = per_point + ap, fixed + af
     nb = (int(df_obj.deriv_work_bytes) - fixed) // per_point
     if nb < 1:
         raise ValueError(f"deriv_work_bytes = {df_obj.deriv_work_bytes} is below one grid point "
@@ -1440,6 +1487,118 @@ def _get_kin(df_obj, kpts):
     gamma = np.abs(kp).max(axis=1) < 1e-12
     t[gamma] = t[gamma].real
     return t[0] if single else t
+
+
+def _xc_call(df_obj, fn, drho, nset, ng, want_e=True):
+    """fisdf_xc_eval on a device density (nset, 4, ng) or (nset, ng) complex: device (e, wv),
+    real."""
+    d = df_obj.device
+    gga = fn.code == _xc.GGA
+    e = d.empty((nset, ng), "f64") if want_e else None
+    wv = d.empty((nset, 4, ng) if gga else (nset, ng), "f64")
+    d.ctx.call("fisdf_xc_eval", fn.code, fn.cx, fn.cc, float(df_obj.xc_rho_cut), _lib.ptr(drho),
+               (4 if gga else 1) * ng, ng, ng, nset, _lib.ptr(e) if want_e else None, ng,
+               _lib.ptr(wv), (4 if gga else 1) * ng, ng)
+    return e, wv
+
+
+def _eval_xc(df_obj, xc, rho):
+    fn = _xc.parse_xc(xc)
+    if fn.family is None:
+        raise ValueError(f"eval_xc: {xc!r} has no local part")
+    gga = fn.code == _xc.GGA
+    r = np.asarray(rho)
+    tail = 2 if gga else 1
+    if r.ndim not in (tail, tail + 1) or (gga and r.shape[-2] != 4) or r.size == 0:
+        want = "(4, n) or (nset, 4, n)" if gga else "(n,) or (nset, n)"
+        raise ValueError(f"eval_xc: rho of shape {r.shape} is not {want} for a "
+                         f"{fn.family} functional")
+    has_set = r.ndim == tail + 1
+    ng = r.shape[-1]
+    r = np.ascontiguousarray(r.reshape((-1,) + r.shape[-tail:]), dtype=np.complex128)
+    nset = r.shape[0]
+    d = df_obj.device
+    dr = d.to_dev(r)
+    e, wv = _xc_call(df_obj, fn, dr, nset, ng)
+    e, wv = d.to_host(e), d.to_host(wv)
+    return (e, wv) if has_set else (e[0], wv[0])
+
+
+def _nr_rks_plan(df_obj, nset):
+    """_deriv_plan of the k-mesh with the arena of the fused block inside the budget.  The fixed
+    part is taken at the whole grid: it does not decrease with the block."""
+    ngrid = int(np.prod(df_obj.mesh))
+    return _deriv_plan(df_obj, None,
+                       arena=lambda nk, nao: _xc.nr_rks_arena(nk, ngrid, nao, nset))
+
+
+def _nr_rks(df_obj, xc, dm, hermi):
+    fn = xc if callable(xc) else _xc.parse_xc(xc)
+    if hermi != 1:
+        raise ValueError(f"nr_rks: hermi must be 1 (Hermitian density matrices), not {hermi!r}")
+    df_obj._kmesh()
+    nk = int(np.prod(df_obj.kmesh))
+    single = np.ndim(dm) < 4
+
+    def shaped(nelec, exc, vxc):
+        return (float(nelec[0]), float(exc[0]), vxc[0]) if single else (nelec, exc, vxc)
+
+    if not callable(fn) and not fn.local:       # nothing local: the device is not touched
+        dms = _format_dms(dm, nk)
+        return shaped(np.zeros(len(dms)), np.zeros(len(dms)), np.zeros(dms.shape, complex))
+    d = df_obj.device
+    if d.sharded(df_obj):
+        raise NotImplementedError("nr_rks on a k-sharded object")
+    dms, ddms = _dms_to_dev(df_obj, dm)
+    nset, nao = dms.shape[0], dms.shape[-1]
+    ngrid = int(np.prod(df_obj.mesh))
+    scale = df_obj.cell.vol / ngrid
+    cut = float(df_obj.xc_rho_cut)
+    if not callable(fn) and fn.code == _xc.LDA:
+        f = df_obj._grid_aos()
+        rho = d.empty((nset, ngrid))
+        d.ctx.call("fisdf_get_rho", _lib.ptr(f), ngrid * nao, nk, ngrid, nao, _lib.ptr(ddms), nset,
+                   _lib.ptr(rho))
+        e, wv = _xc_call(df_obj, fn, rho, nset, ngrid)
+        vxc = d.empty((nset, nk, nao, nao))
+        dv = wv.to(d.torch.complex128)
+        d.ctx.call("fisdf_weighted_gram", _lib.ptr(f), ngrid * nao, nk, ngrid, nao,
+                   _lib.ptr(dv), nset, 0, scale, _lib.ptr(vxc))
+        n = d.to_host(rho).real
+        nelec = scale * np.where(n > cut, n, 0.0).sum(axis=1)
+        return shaped(nelec, scale * d.to_host(e).sum(axis=1), d.to_host(vxc))
+    plan = _nr_rks_plan(df_obj, nset)
+    vxc = d.empty((nset, nk, nao, nao))
+    if not callable(fn):
+        sums = d.empty((nset, 2), "f64")
+        for g0, g1, f4 in _deriv_blocks(df_obj, plan):
+            nb = g1 - g0
+            d.ctx.call("fisdf_nr_rks_block", fn.code, fn.cx, fn.cc, cut, _lib.ptr(f4),
+                       4 * nb * nao, nb * nao, nk, nb, nao, _lib.ptr(ddms), nset, scale,
+                       1 if g0 else 0, _lib.ptr(vxc), _lib.ptr(sums))
+        s = d.to_host(sums)
+        return shaped(s[:, 0].copy(), s[:, 1].copy(), d.to_host(vxc))
+    nelec, exc = np.zeros(nset), np.zeros(nset)
+    for g0, g1, f4 in _deriv_blocks(df_obj, plan):
+        nb = g1 - g0
+        rho = d.empty((nset, 4, nb))
+        d.ctx.call("fisdf_get_rho_gga", _lib.ptr(f4), 4 * nb * nao, nb * nao, nk, nb, nao,
+                   _lib.ptr(ddms), nset, 1, _lib.ptr(rho), nb)
+        rh = np.ascontiguousarray(d.to_host(rho).real)
+        wv = np.empty((nset, 4, nb))
+        for s in range(nset):
+            e, w = fn(rh[s])
+            e, w = np.asarray(e, float), np.asarray(w, float)
+            if e.shape != (nb,) or w.shape != (4, nb):
+                raise ValueError(f"nr_rks: the functional returned e {e.shape} and wv {w.shape} "
+                                 f"for rho (4, {nb}); expected ({nb},) and (4, {nb})")
+            wv[s] = w
+            nelec[s] += scale * rh[s, 0].sum()
+            exc[s] += scale * e.sum()
+        dw = d.to_dev(wv)
+        d.ctx.call("fisdf_gga_gram", _lib.ptr(f4), 4 * nb * nao, nb * nao, nk, nb, nao,
+                   _lib.ptr(dw), 4 * nb, nb, nset, scale, 1 if g0 else 0, _lib.ptr(vxc))
+    return shaped(nelec, exc, d.to_host(vxc))
 
 
 def _get_pp(df_obj, kpts, nuc):

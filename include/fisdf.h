@@ -599,6 +599,48 @@ int fisdf_get_rho_gga(fisdf_ctx* ctx, const void* d_f4, long f_kstride, long f_c
 int fisdf_gga_gram(fisdf_ctx* ctx, const void* d_f4, long f_kstride, long f_cstride, int nk, int ng,
                    int nao, const void* d_w, long w_sstride, long w_cstride, int nset, double scale,
                    int accumulate, void* d_out);
+/* ---- the spin-unpolarised functional at the points of a block, and the fused RKS block --------
+ * LDA: Slater exchange + PW92 correlation (libxc's "pw_mod" parameters); GGA: PBE.  With
+ * n = Re rho_0, d_c n = Re rho_c (imaginary parts are not read) and sigma = |grad n|^2:
+ *   d_e[s e_sstride + g]                 = cx e_x + cc e_c, the energy per unit volume
+ *                                          (E_xc = (vol/ngrid) sum_g e)
+ *   d_wv[s w_sstride + g]                = d e / d n
+ *   d_wv[s w_sstride + c w_cstride + g]  = 2 d e / d sigma  d_c n,  c = 1..3 (GGA only)
+ * — the unweighted wv of fisdf_gga_gram (LDA: the v of fisdf_weighted_gram, as real doubles).
+ * d_rho[s rho_sstride + c rho_cstride + g] complex: fisdf_get_rho_gga's layout is rho_sstride =
+ * 4 rho_cstride (GGA), fisdf_get_rho's rho_sstride = ngrid (LDA, rho_cstride and w_cstride not
+ * read).  Minimum strides: LDA every set stride >= ng; GGA component strides >= ng and set strides
+ * >= 3 component strides + ng; e_sstride >= ng.  A point with n <= rho_cut (negative or NaN n
+ * included) gets e = 0 and wv = 0 exactly.  d_e or d_wv may be NULL and is then skipped.  FP64,
+ * analytic derivatives in s^2 and t^2 (sigma = 0 is no special case); one point per thread, no
+ * reduction: repeated calls agree bit for bit.  Refused on the host with the outputs untouched:
+ * an unknown family, ng or nset < 1, a stride below its minimum, rho_cut negative or NaN, cx or cc
+ * not finite.  Asynchronous. */
+#define FISDF_XC_LDA 0
+#define FISDF_XC_GGA 1
+int fisdf_xc_eval(fisdf_ctx* ctx, int family, double cx, double cc, double rho_cut,
+                  const void* d_rho, long rho_sstride, long rho_cstride, int ng, int nset,
+                  void* d_e, long e_sstride, void* d_wv, long w_sstride, long w_cstride);
+/* One block of a Kohn-Sham XC step (PySCF KNumInt.nr_rks), three stages back to back on the
+ * context's stream over one block d_f4 of fisdf_eval_ao_deriv1 output: fisdf_get_rho_gga with
+ * hermi = 1 into the arena, the functional above, and fisdf_gga_gram of its wv into
+ * d_vxc (nset, nk, nao, nao) — the bits of the three entries called one after another.  Also
+ * d_sums[s] = scale (sum_g n, sum_g e), doubles (nset, 2): n as the functional saw it (points at
+ * or below the cut add nothing to either), summed by a tree per 256 points and then over the
+ * workgroups in a fixed order, no atomics.  accumulate = 0 overwrites d_vxc and d_sums, else adds
+ * to what they hold.  family must be FISDF_XC_GGA.  The arena is carved once for all three stages
+ * (fisdf_nr_rks_plan); the argument checks of all three stages (family, sizes, strides, cx, cc,
+ * rho_cut, scale, null pointers) run before the first launch, and a call they refuse leaves d_vxc
+ * and d_sums untouched.  Asynchronous. */
+int fisdf_nr_rks_block(fisdf_ctx* ctx, int family, double cx, double cc, double rho_cut,
+                       const void* d_f4, long f_kstride, long f_cstride, int nk, int ng, int nao,
+                       const void* d_dms, int nset, double scale, int accumulate, void* d_vxc,
+                       void* d_sums);
+/* The arena of fisdf_nr_rks_block, no context needed: at most *h_point_bytes ng + *h_fixed_bytes
+ * bytes.  Per point 64 B of rho, 32 B of wv and 8 B of e a set and the gram's 16 nk nao B; fixed:
+ * the gram's matrix and split-K partials for this ng, the workgroup sums and the alignment of the
+ * seven pieces.  *h_fixed_bytes does not decrease with ng. */
+int fisdf_nr_rks_plan(int nk, int ng, int nao, int nset, long* h_point_bytes, long* h_fixed_bytes);
 /* The three stages back to back with scale = vol / ngrid: d_vj (nset, nk, nao, nao) for the
  * k-mesh, or, with d_fband (nband, ngrid, nao) the AOs at band k-points on the same grid,
  * d_vj (nset, nband, nao, nao) at those (d_fband NULL: the k-mesh).  rho and v live in the
